@@ -12,10 +12,15 @@ N GPUs:       python -m torch.distributed.run --nproc-per-node N bench.py --gpus
               gradients all-reduced over RCCL; value = N * iterations/s, i.e.
               batch-256-equivalent gradient steps per second, weak scaling).
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (dominant kernel = the
-grouped fp32 MFMA GEMM, timed with HIP events on its launch stream) and
-`cpu_baseline` (the oracle's torch-CPU port of the reference update + deque replay
-on this host's cores, bounded sample).
+Prints ONE JSON line (rank 0).  A plain run does only what the headline figure needs: it
+fills the replay, warms up, times --steps updates once and prints the line (`value`,
+`ms_per_step`).  --dump-outputs DIR also writes what the last timed update left (the timed
+updates' losses, every network's parameters, log_alpha) as DIR/<name>.npy.  --full adds
+everything else: several timed windows (median reported), the one-update-per-launch and
+API-faithful rates, `roofline` (dominant kernel = the grouped fp32 MFMA GEMM, timed with
+HIP events on its launch stream), the trainer loop, `cpu_baseline` (the oracle's torch-CPU
+port of the reference update + deque replay on this host's cores, bounded sample) and, data
+parallel, the other optimizer form (`dp_form_ab`); a plain line carries null there.
 """
 from __future__ import annotations
 
@@ -373,8 +378,13 @@ def roofline_object(ctx, args, wl, peak, data_parallel=False, step_us_real=None)
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=200,
+                    help="timed updates per window (any number: the losses are fetched every "
+                         f"{LOSS_RING} updates inside the window)")
+    ap.add_argument("--warmup", type=int, default=50,
+                    help="untimed updates before the first window; beside them every graph the "
+                         "window replays (--updates-per-launch updates and the remainder of "
+                         f"--steps) runs once before and {SETTLE_PASSES} times after them, untimed")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS),
                     help="BASELINE.json configs[1] (2: batch 256 uniform), configs[2] "
                          "(3: batch 4096, prioritized replay in HBM) or configs[4] per GPU "
@@ -385,9 +395,18 @@ def parse_args(argv=None):
                     help="GEMM operand arithmetic (default: the config's)")
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--fill", type=int, default=1_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: several timed "
+                         "windows, one-update-per-launch and API-faithful rates, roofline, "
+                         "trainer loop, CPU baseline, the other data-parallel optimizer form "
+                         "(each with its own --no-* switch); off: one window of --steps updates")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed updates write what they computed (their losses, every "
+                         "network's parameters, log_alpha) as DIR/<name>.npy")
     ap.add_argument("--windows", type=int, default=0,
-                    help="timed windows of --steps updates each (median reported); 0: enough "
-                         "windows for >= 2000 timed updates (at least 5)")
+                    help="timed windows of --steps updates each (median reported); 0: one "
+                         "window, or with --full enough windows for >= 2000 timed updates (at "
+                         "least 5)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -415,8 +434,12 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.batch is None:                 # both the single-GPU and the DP paths use it
         args.batch = CONFIGS[args.config]["batch"]
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.windows <= 0:
-        args.windows = min(200, max(5, -(-2000 // max(1, args.steps))))
+        args.windows = min(200, max(5, -(-2000 // args.steps))) if args.full else 1
+    if not args.full:                      # a plain run: the headline figure alone
+        args.no_cpu_baseline = args.no_roofline = args.no_trainer_loop = True
     return args
 
 
@@ -424,6 +447,74 @@ def graph_sizes(steps, per_launch):
     """Updates per launch of every launch the timed loop of `steps` updates makes."""
     full, rem = divmod(steps, per_launch)
     return sorted({n for n in ((per_launch if full else 0), rem) if n > 0})
+
+
+DUMP_MAX_BYTES = 64 << 20
+SETTLE_PASSES = 4           # untimed launches of every timed graph after the warm-up
+LOSS_RING = 4096            # updates whose losses the library keeps for sacmi_fetch_losses
+
+
+def launches(n, per_launch):
+    """Updates per launch of `n` updates, in order: the trainer's `for _ in
+    range(updates_per_step)` loop, `per_launch` updates per launch and the remainder."""
+    full, rem = divmod(n, per_launch)
+    return [per_launch] * full + ([rem] if rem else [])
+
+
+def untimed_launches(steps, warmup, per_launch):
+    """Every launch before the first timed window, in order: each graph the window replays
+    once (captured and instantiated there, whatever --warmup is), the --warmup updates, then
+    SETTLE_PASSES times each of those graphs in the window's order."""
+    sizes = graph_sizes(steps, per_launch)
+    return sizes + launches(warmup, per_launch) + SETTLE_PASSES * sizes[::-1]
+
+
+def fetch_chunks(steps, per_launch, ring=LOSS_RING):
+    """Updates between two fetches of the losses inside a timed window: the library keeps
+    the last `ring` updates' losses, so a longer window fetches every `ring` updates (rounded
+    down to whole launches: the window's launches are those of launches(steps))."""
+    chunk = ring // per_launch * per_launch
+    return [chunk] * (steps // chunk) + ([steps % chunk] if steps % chunk else [])
+
+
+def final_outputs(ctx, losses) -> dict:
+    """What a caller of the timed path holds after its last update: the losses it fetched
+    (one row per timed update of the last window: q1, q2, policy) and the state the update
+    left — every network's parameters and log_alpha."""
+    from sacmi import _lib as L
+    from sacmi.core import NET_IDS
+    out = {"losses": np.asarray(losses, np.float32).reshape(-1, 3)}
+    for net in NET_IDS:
+        for key, val in ctx.get_net(net).items():
+            out[f"{net}.{key}"] = val
+    out["log_alpha"] = np.array([ctx.get_scalar(L.S_LOG_ALPHA)], np.float64)
+    return out
+
+
+def dump_outputs(dirname, arrays, max_bytes=DUMP_MAX_BYTES) -> dict:
+    """Write every array as dirname/<name>.npy (float32 and float64 as they are, anything
+    else as float64).  At most max_bytes in all: beyond that the small arrays (together at
+    most a quarter of the limit: scalars, losses, biases) stay whole and every other array
+    keeps the same share of its elements, a fixed sample (sorted flat indices from
+    default_rng([0, i]), i the array's rank by name: the same from run to run).  Returns
+    {name: elements written}."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64)
+                                      else v.astype(np.float64))
+              for k, v in ((k, np.asarray(v)) for k, v in arrays.items())}
+    total = sum(a.nbytes for a in arrays.values())
+    small = max_bytes // (4 * max(len(arrays), 1))
+    whole = sum(a.nbytes for a in arrays.values() if a.nbytes <= small)
+    keep = 1.0 if total <= max_bytes else (max_bytes - whole) / (total - whole)
+    written = {}
+    for i, (name, a) in enumerate(sorted(arrays.items())):
+        if keep < 1.0 and a.nbytes > small:
+            n = int(a.size * keep)
+            pick = np.sort(np.random.default_rng([0, i]).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
 
 
 _RESULT_FD = None   # the process's original stdout while fd 1 is routed to stderr
@@ -485,33 +576,38 @@ def main():
     upl = max(1, min(args.updates_per_launch, 256))
 
     def run_updates(n):
-        # the trainer's `for _ in range(updates_per_step)` loop: `upl` updates per launch
-        full, rem = divmod(n, upl)
-        for _ in range(full):
-            ctx.step_many_async(args.batch, upl)
-        if rem:
-            ctx.step_many_async(args.batch, rem)
+        for k in launches(n, upl):
+            ctx.step_many_async(args.batch, k)
 
-    # every graph the timed loop replays is captured, instantiated and replayed once
-    # before the first timed window, whatever --warmup is
-    for n in graph_sizes(args.steps, upl):
-        ctx.step_many_async(args.batch, n)
-    run_updates(args.warmup)
+    # after a short warm-up alone the first timed window is slower than every later one
+    # (consecutive 20-update windows: 3.28, 2.29, 2.26, 2.24 ms, then 2.22-2.25 ms; one
+    # measurement on one MI355X): untimed_launches ends with SETTLE_PASSES replays of the
+    # window's graphs, so that the first window starts where a window leaves off
+    for k in untimed_launches(args.steps, args.warmup, upl):
+        ctx.step_many_async(args.batch, k)
+    ctx.fetch_losses(min(args.steps, LOSS_RING))       # the window's fetch, once untimed
     ctx.synchronize()
     torch.cuda.synchronize()
+    last = {}
 
     def window():
         t0 = time.perf_counter()
-        run_updates(args.steps)
-        losses = ctx.fetch_losses(args.steps)      # D2H of every loss, inside the timed region
+        rows = []
+        for n in fetch_chunks(args.steps, upl):
+            run_updates(n)
+            rows.append(ctx.fetch_losses(n))       # D2H of every loss, inside the timed region
         ctx.synchronize()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        losses = np.concatenate(rows)
         assert losses.shape == (args.steps, 3) and np.all(np.isfinite(losses)), losses[-3:]
+        last["losses"] = losses
         return dt
 
     dt, dts = median_windows(window, args.windows)
     graphs = ctx.get_scalar(L.S_GRAPH_COUNT)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, final_outputs(ctx, last["losses"]))
     if args.profile_only:
         emit(json.dumps({"steps": args.steps, "windows": args.windows,
                          "ms_per_step": 1e3 * dt / args.steps}))
@@ -520,20 +616,22 @@ def main():
 
     # one update per launch (update_parameters_async), and the API-faithful mode with
     # the losses synced every update (sac_imp.py:140-144 .item())
-    n_one = max(200, args.steps // 2)      # (~30 ms: host scheduling noise averages out)
-    ctx.step_async(args.batch)
-    ctx.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(n_one):
+    one_sps = sync_sps = None
+    if args.full:
+        n_one = max(200, args.steps // 2)      # (~30 ms: host scheduling noise averages out)
         ctx.step_async(args.batch)
-    ctx.fetch_losses(n_one)
-    ctx.synchronize()
-    one_sps = n_one / (time.perf_counter() - t1)
-    n_sync = max(200, args.steps // 4)
-    t1 = time.perf_counter()
-    for _ in range(n_sync):
-        ctx.step(args.batch)
-    sync_sps = n_sync / (time.perf_counter() - t1)
+        ctx.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(n_one):
+            ctx.step_async(args.batch)
+        ctx.fetch_losses(n_one)
+        ctx.synchronize()
+        one_sps = n_one / (time.perf_counter() - t1)
+        n_sync = max(200, args.steps // 4)
+        t1 = time.perf_counter()
+        for _ in range(n_sync):
+            ctx.step(args.batch)
+        sync_sps = n_sync / (time.perf_counter() - t1)
 
     roof = None
     peak = PEAK_BF16_MFMA_TFLOPS if wl["dtype"] == "bf16" else PEAK_FP32_MFMA_TFLOPS
@@ -572,8 +670,9 @@ def main():
                    "global_batch": args.batch, "replay_fill": fill, "parallelism": "single GPU"},
         "updates_per_launch": upl,
         "graphs_cached": int(graphs),
-        "one_update_per_launch_steps_per_s": round(one_sps, 2),
-        "api_faithful_steps_per_s": round(sync_sps, 2),
+        "full": args.full,
+        "one_update_per_launch_steps_per_s": round(one_sps, 2) if args.full else None,
+        "api_faithful_steps_per_s": round(sync_sps, 2) if args.full else None,
         "mfma_util_step": round(flops * sps / 1e12 / peak, 4),
         "necessary_gflop_per_step": round(flops / 1e9, 4),
         "trainer_loop": loop,

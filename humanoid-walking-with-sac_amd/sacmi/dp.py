@@ -134,7 +134,8 @@ def run_dp_bench(args, rank: int, world: int, local_rank: int, emit=print):
     native = not getattr(args, "dp_torch", False)
     # the library's communicator: the native driver's collectives, and the roofline's
     # timeline of the data-parallel sequence (both paths)
-    want_roof = not getattr(args, "no_roofline", False)
+    full = bool(getattr(args, "full", False))       # plain run: the line's own windows alone
+    want_roof = full and not getattr(args, "no_roofline", False)
     sim = int(getattr(args, "dp_sim_world", 0) or 0)
     if sim:                                         # one GPU stands in for `sim` ranks
         # rank 0's work only, in BOTH optimizer forms (SACMI_DP_LOOPBACK_ONE_RANK, read at each
@@ -165,6 +166,11 @@ def run_dp_bench(args, rank: int, world: int, local_rank: int, emit=print):
                 upd(args.batch)
             upd.flush()
     run(args.warmup)
+    if native:      # the window's graphs again, in its order (bench.untimed_launches; the
+                    # windows here fetch no losses, so there is no fetch to rehearse)
+        for _ in range(B.SETTLE_PASSES):
+            for n in reversed(sizes):
+                ctx.step_dp(args.batch, n)
     torch.cuda.synchronize()
 
     def window():
@@ -190,7 +196,12 @@ def run_dp_bench(args, rank: int, world: int, local_rank: int, emit=print):
         dist.all_gather(allchk, chk)
         return all(bool(torch.equal(allchk[0], c)) for c in allchk)
 
-    replicas_ok = replicas_equal()
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        # rank 0's replica after the last timed update, and the losses of its own batches
+        # (the window's last min(steps, LOSS_RING) updates: these windows fetch none)
+        B.dump_outputs(args.dump_outputs,
+                       B.final_outputs(ctx, ctx.fetch_losses(min(args.steps, B.LOSS_RING))))
+    replicas_ok = replicas_equal() if full else None
     peak = B.PEAK_BF16_MFMA_TFLOPS if wl["dtype"] == "bf16" else B.PEAK_FP32_MFMA_TFLOPS
     roof = None
     if want_roof:
@@ -203,7 +214,7 @@ def run_dp_bench(args, rank: int, world: int, local_rank: int, emit=print):
     # (ZeRO-1) form over real RCCL ranks (SACMI_BENCH_DP_FORM_AB=0: skipped)
     form_ab = None
     phases = world > 1 or sim or os.environ.get("SACMI_DP_PHASES_AT_WORLD1") is not None
-    if native and phases and os.environ.get("SACMI_BENCH_DP_FORM_AB", "1") != "0":
+    if full and native and phases and os.environ.get("SACMI_BENCH_DP_FORM_AB", "1") != "0":
         was = ctx.dp_sharded()
         form_ab = {"form": "sharded" if not was else "all-reduce"}
         # the switch and the first launch of each graph (its capture) are where one rank can
@@ -249,7 +260,7 @@ def run_dp_bench(args, rank: int, world: int, local_rank: int, emit=print):
                 torch.cuda.synchronize()
     cpu = None
     # (the CPU baseline is timed on rank 0 at N = 1 only: the N > 1 lines carry none)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         n_cpu = min(fill * world, 1_000_000)
         cpu_rows = tuple(x[:n_cpu] for x in B.synth(n_cpu, 7, S, A))
         cpu = B.cpu_baseline(cpu_rows, seconds=args.cpu_seconds, batch=args.batch, per=per,
@@ -275,7 +286,7 @@ def run_dp_bench(args, rank: int, world: int, local_rank: int, emit=print):
                        "state_dim": S, "action_dim": A, "hidden": H, "n_hidden": wl["n_hidden"],
                        "global_batch": args.batch * world, "replay_fill": fill * world,
                        "replay": wl["replay"], "parallelism": f"dp{world}"},
-            "iterations_per_s": round(iters, 2),
+            "iterations_per_s": round(iters, 2), "full": full,
             "updates_per_launch": per_launch if native else 1,
             "dp_graph": native,
             "dp_driver": "library (sacmi_step_dp: RCCL issued by libsacmi)" if native

@@ -45,13 +45,13 @@ def test_abi_version_and_error_string():
     assert isinstance(lib.sacmi_last_error(), bytes)
 
 
-def test_config_struct_layout_matches_header():
+def test_config_struct_layout_matches_header(tmp_path):
     """The ctypes mirror must have the C struct's size (checked with gcc)."""
     from sacmi import _lib as L
     src = ('#include "sacmi.h"\n#include <stdio.h>\n'
            'int main(){printf("%zu\\n", sizeof(sacmi_config));return 0;}\n')
-    tmp = os.path.join("/tmp", "sacmi_sizeof.c")
-    exe = os.path.join("/tmp", "sacmi_sizeof")
+    tmp = str(tmp_path / "sacmi_sizeof.c")
+    exe = str(tmp_path / "sacmi_sizeof")
     open(tmp, "w").write(src)
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), tmp, "-o", exe], check=True)
     size = int(subprocess.run([exe], capture_output=True, text=True, check=True).stdout)

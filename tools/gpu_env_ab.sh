@@ -10,7 +10,7 @@ for r in $(seq 1 ${REPS:-2}); do
   for e in ${ENVS:-default}; do
     n=$(echo $e | tr '=' '_')
     if [ "$e" = default ]; then e=""; fi
-    timeout -k 10 200 env $e python3 bench.py --no-trainer-loop --no-cpu-baseline --config ${CONFIG:-2} \
+    timeout -k 10 200 env $e python3 bench.py --full --no-trainer-loop --no-cpu-baseline --config ${CONFIG:-2} \
       > $O/${n}_$r.json 2> $O/${n}_$r.err || { tail $O/${n}_$r.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$O/${n}_$r.json')); r=d.get('roofline') or {}

@@ -10,7 +10,7 @@ mkdir -p $O
 for r in $(seq 1 ${REPS:-1}); do
   for v in ${LIBS:-main}; do
     if [ "$v" = main ]; then L=""; else L="$GRAFT_REPO_ROOT/humanoid-walking-with-sac_amd/sacmi/libsacmi_$v.so"; fi
-    SACMI_LIB_PATH=$L timeout -k 10 200 python3 bench.py --no-trainer-loop --no-cpu-baseline --config ${CONFIG:-2} \
+    SACMI_LIB_PATH=$L timeout -k 10 200 python3 bench.py --full --no-trainer-loop --no-cpu-baseline --config ${CONFIG:-2} \
       ${BENCH_ARGS:-} > $O/${v}_$r.json 2> $O/${v}_$r.err || { tail $O/${v}_$r.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$O/${v}_$r.json')); r=d.get('roofline') or {}

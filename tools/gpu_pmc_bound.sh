@@ -19,7 +19,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 TAG=${1:-c5}; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmcb_$TAG
-ARGS=${*:---config 5 --steps 20 --warmup 5 --profile-only}
+ARGS=${*:---full --config 5 --steps 20 --warmup 5 --profile-only}
 mkdir -p $OUT
 cd /tmp
 i=0

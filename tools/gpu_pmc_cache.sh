@@ -11,7 +11,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 TAG=${1:-c2}; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmcc_$TAG
-ARGS=${*:---steps 20 --warmup 5 --profile-only}
+ARGS=${*:---full --steps 20 --warmup 5 --profile-only}
 mkdir -p $OUT
 cd /tmp
 i=0

@@ -9,7 +9,7 @@
 #   dpab     the data-parallel bench at one rank over real RCCL with the phase sequence forced
 #            (SACMI_DP_PHASES_AT_WORLD1): the line's form and the other one (dp_form_ab);
 #            dpabr the same with the sharded form as the line's
-#   driver   `python3 bench.py` with no arguments (the driver's round-end line)
+#   driver   `python3 bench.py --full` with no other arguments (every measurement of the line)
 #   pmcb     the bound-analysis PMC passes (tools/gpu_pmc_bound.sh) of CONFIGS_PMCB ("5 3")
 #   prof     the round's profile set (tools/gpu_profile.sh: PMC passes of CONFIGS, the
 #            rocprofv3 kernel-trace summary of the driver's config-2 command)
@@ -19,7 +19,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/${TAG:-session}
 mkdir -p $O
-B="python3 bench.py --no-trainer-loop --no-cpu-baseline"
+B="python3 bench.py --full --no-trainer-loop --no-cpu-baseline"
 line() { python3 -c "
 import json; d=json.load(open('$1')); r=d.get('roofline') or {}
 print('$1', d['value'], d['ms_per_step'], r.get('frac'), {k: v for k, v in (r.get('sites_us') or {}).items() if 'L' in k or 'chain' in k})"; }
@@ -56,11 +56,11 @@ for step in ${STEPS:-tests smoke configs}; do
       line $O/$f.json
       python3 -c "import json; d=json.load(open('$O/$f.json')); print(d['dp_optimizer_step'], d['replicas_bitwise_equal'], d['dp_form_ab'])" ;;
     driver)   # the driver's own round-end command (defaults: trainer loop and cpu_baseline included)
-      timeout -k 10 600 python3 bench.py > $O/driver_bench.json 2> $O/driver_bench.err || { tail $O/driver_bench.err; exit 1; }
+      timeout -k 10 600 python3 bench.py --full > $O/driver_bench.json 2> $O/driver_bench.err || { tail $O/driver_bench.err; exit 1; }
       line $O/driver_bench.json ;;
     pmcb)
       for c in ${CONFIGS_PMCB:-5 3}; do
-        bash tools/gpu_pmc_bound.sh c$c --config $c --steps 20 --warmup 5 --profile-only || exit 1
+        bash tools/gpu_pmc_bound.sh c$c --full --config $c --steps 20 --warmup 5 --profile-only || exit 1
         cp gpurun_out/pmc_bound_c$c.json gpurun_out/pmc_bound_c$c.txt $O/ || exit 1
       done ;;
     prof)

@@ -12,6 +12,6 @@ timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke
 timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/b_driver.json 2> $O/b_driver.err || { tail $O/b_driver.err; exit 1; }
 cat $O/b_driver.json | cut -c1-600
 [ -n "${SKIP_CONFIGS:-}" ] && exit 0
-timeout -k 10 400 python3 bench.py --config 3 --no-trainer-loop > $O/b_c3.json 2> $O/b_c3.err || { tail $O/b_c3.err; exit 1; }
-timeout -k 10 400 python3 bench.py --config 5 --no-trainer-loop > $O/b_c5.json 2> $O/b_c5.err || { tail $O/b_c5.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config 3 --no-trainer-loop > $O/b_c3.json 2> $O/b_c3.err || { tail $O/b_c3.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config 5 --no-trainer-loop > $O/b_c5.json 2> $O/b_c5.err || { tail $O/b_c5.err; exit 1; }
 cut -c1-300 $O/b_c3.json $O/b_c5.json
