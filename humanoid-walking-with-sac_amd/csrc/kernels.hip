@@ -1445,6 +1445,40 @@ __device__ __forceinline__ u2v pack_bf16x4(float4 v) {
   return __builtin_bit_cast(u2v, x);
 }
 
+// ---- pieces the batch-4096-class kernels share (k_fwd16 .. k_axk_x6) ----
+
+// the descriptor p whose tile range holds workgroup tile `bid`, and the tile's index t in
+// it; false when t is past the descriptor's tiles (a grid padded past the level)
+__device__ __forceinline__ bool level_tile(const GemmBatch& batch, int bid, int& p, int& t) {
+  p = 0;
+  for (int q = 1; q < batch.count; ++q)
+    if (bid >= batch.d[q].tile_begin) p = q;
+  t = bid - batch.d[p].tile_begin;
+  return t < batch.d[p].tiles_m * batch.d[p].tiles_n;
+}
+
+// four consecutive elements of an operand row, the first at index i0: those at or past lim
+// (they read the row's next columns, or a clamped address) zeroed — all four where !row_ok
+__device__ __forceinline__ float4 mask4(float4 x, int i0, int lim, bool row_ok = true) {
+  x.x = row_ok && i0 < lim ? x.x : 0.f;     x.y = row_ok && i0 + 1 < lim ? x.y : 0.f;
+  x.z = row_ok && i0 + 2 < lim ? x.z : 0.f; x.w = row_ok && i0 + 3 < lim ? x.w : 0.f;
+  return x;
+}
+// the same for four packed bf16
+__device__ __forceinline__ uint2 mask4h(uint2 x, int i0, int lim, bool row_ok = true) {
+  x.x = (row_ok && i0 < lim ? x.x & 0xffffu : 0u) | (row_ok && i0 + 1 < lim ? x.x & 0xffff0000u : 0u);
+  x.y = (row_ok && i0 + 2 < lim ? x.y & 0xffffu : 0u) | (row_ok && i0 + 3 < lim ? x.y & 0xffff0000u : 0u);
+  return x;
+}
+
+template <int MI, int NT>
+__device__ __forceinline__ void zero_acc(f4 (&acc)[MI][NT]) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+}
+
 // AH (act16): A is bf16 (4 k per 8-byte load, straight into the slab) and C is bf16.
 // Waves: 2 x fwd16_wc<kFBN>() of 64 x (kFBN / wc) sub-tiles
 // 8 waves (4 per SIMD at two workgroups per CU) hide each other's LDS / barrier latency
@@ -1467,14 +1501,9 @@ __global__ __launch_bounds__(64 * fwd16_waves<kFBN>(), 2) void k_fwd16(GemmBatch
   constexpr int NB = kFBN / RPP;         // B rows staged per thread
   __shared__ __attribute__((aligned(16))) __bf16 sA[2][kFBM][LDR];
   __shared__ __attribute__((aligned(16))) __bf16 sB[2][kFBN][LDR];
-  const int bid = blockIdx.x;
-  int p = 0;
-  for (int q = 1; q < batch.count; ++q)
-    if (bid >= batch.d[q].tile_begin) p = q;
+  int p, t, tr, tc;
+  if (!level_tile(batch, blockIdx.x, p, t)) return;
   const GemmDesc& d = batch.d[p];
-  const int t = bid - d.tile_begin;
-  if (t >= d.tiles_m * d.tiles_n) return;
-  int tr, tc;
   place_tile(d, t, tr, tc);
   const int m0 = tr * kFBM, n0 = tc * kFBN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1498,31 +1527,22 @@ __global__ __launch_bounds__(64 * fwd16_waves<kFBN>(), 2) void k_fwd16(GemmBatch
   uint2 gah[AH ? NA : 1];             // AH: A rows in bf16, 4 k per 8 bytes
   uint2 gh[BH ? NB : 1];              // BH: B from its bf16 shadow, 4 k per 8 bytes
   const rsrc_t rBh = make_rsrc(BH ? reinterpret_cast<const float*>(d.Bh) : d.B, 0x7fffffffu);
-  auto zk = [&](float4 x, int k) {    // elements past K read the row's next columns: zeroed
-    x.x = k < K ? x.x : 0.f; x.y = k + 1 < K ? x.y : 0.f; x.z = k + 2 < K ? x.z : 0.f; x.w = k + 3 < K ? x.w : 0.f;
-    return x;
-  };
-  auto zkh = [&](uint2 x, int k) {
-    x.x = (k < K ? x.x & 0xffffu : 0u) | (k + 1 < K ? x.x & 0xffff0000u : 0u);
-    x.y = (k + 2 < K ? x.y & 0xffffu : 0u) | (k + 3 < K ? x.y & 0xffff0000u : 0u);
-    return x;
-  };
   auto gload = [&](int k0) {
     const int k = k0 + kq;
     const uint32_t ko = (uint32_t)(k < K ? k : 0) * 4u;
     if constexpr (AH) {
 #pragma unroll
-      for (int i = 0; i < NA; ++i) gah[i] = zkh(buf_ld2(rA, offA[i] + ko / 2u), k);
+      for (int i = 0; i < NA; ++i) gah[i] = mask4h(buf_ld2(rA, offA[i] + ko / 2u), k, K);
     } else {
 #pragma unroll
-      for (int i = 0; i < NA; ++i) ga[i] = zk(buf_ld4(rA, offA[i] + ko), k);
+      for (int i = 0; i < NA; ++i) ga[i] = mask4(buf_ld4(rA, offA[i] + ko), k, K);
     }
     if constexpr (BH) {
 #pragma unroll
-      for (int i = 0; i < NB; ++i) gh[i] = zkh(buf_ld2(rBh, offB[i] / 2u + ko / 2u), k);
+      for (int i = 0; i < NB; ++i) gh[i] = mask4h(buf_ld2(rBh, offB[i] / 2u + ko / 2u), k, K);
     } else {
 #pragma unroll
-      for (int i = 0; i < NB; ++i) gb[i] = zk(buf_ld4(rB, offB[i] + ko), k);
+      for (int i = 0; i < NB; ++i) gb[i] = mask4(buf_ld4(rB, offB[i] + ko), k, K);
     }
   };
   auto swrite = [&](int buf) {
@@ -1538,10 +1558,7 @@ __global__ __launch_bounds__(64 * fwd16_waves<kFBN>(), 2) void k_fwd16(GemmBatch
     }
   };
   f4 acc[MI][NT];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   FwdEpi<NT, MI> ep;
   ep.load(d, n0 + wn, lane);
   gload(0);
@@ -1578,9 +1595,12 @@ __global__ __launch_bounds__(64 * fwd16_waves<kFBN>(), 2) void k_fwd16(GemmBatch
 // top 8 significant bits; m: the next 8 of the remainder; l: the rest, at most 8 bits — both
 // subtractions exact in fp32), once per workgroup as the slab is staged, into three bf16 LDS
 // planes per operand.  a.b is then 9 cross products of exact parts; the 6 kept (hh, hm, mh,
-// mm, hl, lh) are exact in the fp32 accumulator, the 3 dropped (ml, lm, ll) are below
-// 2^-25 |a b| — under fp32's own unit roundoff: the result is as accurate as the fp32 MFMA
-// chain (rounded differently, not bit-identical).  Per 32 k and 16x16 block: 6
+// mm, hl, lh) are exact products summed in the fp32 accumulator.  With truncation
+// |m| < 2^-7 |x| and |l| < 2^-15 |x|, so the 3 dropped (ml, lm, ll) are bounded by about
+// 2^-21 |a b| per product — some 8 fp32 ulps, not below the unit roundoff — and, every
+// part carrying its operand's sign, they are one-signed: each product is short toward zero,
+// a systematic bias, not rounding noise (and the result is not bit-identical to the fp32
+// MFMA chain's).  Per 32 k and 16x16 block: 6
 // v_mfma_f32_16x16x32_bf16 (16 cycles each) for 8 v_mfma_f32_16x16x4_f32 (32 each).
 // Round 6's register-split form at batch 256 (profiles/r06/x6_ab) paid the split per wave
 // per fragment; here it is paid once per staged element.
@@ -1614,31 +1634,50 @@ __device__ __forceinline__ void x6_split4(float4 v, u2v& h, u2v& m, u2v& l) {
   h = u2v{ph[0], ph[1]}; m = u2v{pm[0], pm[1]}; l = u2v{pl[0], pl[1]};
 }
 
+// four fp32 values split and stored: 8 bytes to the same spot of the h, m and l planes
+__device__ __forceinline__ void x6_store3(__bf16* ph, __bf16* pm, __bf16* pl, float4 v) {
+  u2v h, m, l;
+  x6_split4(v, h, m, l);
+  *reinterpret_cast<u2v*>(ph) = h;
+  *reinterpret_cast<u2v*>(pm) = m;
+  *reinterpret_cast<u2v*>(pl) = l;
+}
+
+// the six kept products of one 16x16x32 block, small terms first into the accumulator (the
+// order is part of the result's bits: one chain for every x6 kernel)
+__device__ __forceinline__ void x6_mfma(f4& acc, bf16x8 ah, bf16x8 am, bf16x8 al, bf16x8 bh,
+                                        bf16x8 bm, bf16x8 bl) {
+  f4 c = acc;
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, c, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+}
+
+// column of element k in row r of a [row][k] plane (k_fwd_x6's planes, k_axk_x6's A planes):
+// 64-B rows, each row's 16-B k chunks stored at chunk ^ ((row >> 2) & 2): the 16 lanes of
+// every ds_read_b128 lane group on 16 distinct 4-bank slots, the two rows of each
+// ds_write_b64 lane group on all 32 banks (profiles/r06/x6_swizzle_ab)
+__device__ __forceinline__ int x6_swz(int r, int k) { return (((k >> 3) ^ ((r >> 2) & 2)) << 3) | (k & 7); }
+
 template <int BN>
 __global__ __launch_bounds__(64 * kX6Waves, 2) void k_fwd_x6(GemmBatch batch) {
   const TlMark tl_mark(batch.tl, TL_FWD_X6);
   constexpr int NWV = kX6Waves, WC = 2, WR = NWV / WC;
   constexpr int MW = kFBM / WR, MI = MW / 16, NW = BN / WC, NT = NW / 16;
   static_assert(NT >= 2 && MI >= 1, "a wave covers whole 32-column dot blocks");
-  // 64-B rows, each row's 16-B k chunks stored at chunk ^ ((row >> 2) & 2): the 16 lanes of
-  // every ds_read_b128 lane group on 16 distinct 4-bank slots, the two rows of each
-  // ds_write_b64 lane group on all 32 banks (profiles/r06/x6_swizzle_ab)
-  constexpr int LDR = kX6K;
+  constexpr int LDR = kX6K;              // 64-B rows, chunks swizzled (x6_swz)
   constexpr int TPR = kX6K / 4;          // staging threads per row (4 k each)
   constexpr int RPP = 64 * NWV / TPR;    // rows per staging pass
   constexpr int NA = kFBM / RPP, NB = BN / RPP;
   static_assert(NA >= 1 && NB >= 1, "staging passes");
   __shared__ __attribute__((aligned(16))) __bf16 sA[3][kFBM][LDR];
   __shared__ __attribute__((aligned(16))) __bf16 sB[3][BN][LDR];
-  auto cw = [](int r, int k) { return (((k >> 3) ^ ((r >> 2) & 2)) << 3) | (k & 7); };
-  const int bid = blockIdx.x;
-  int p = 0;
-  for (int q = 1; q < batch.count; ++q)
-    if (bid >= batch.d[q].tile_begin) p = q;
+  int p, t, tr, tc;
+  if (!level_tile(batch, blockIdx.x, p, t)) return;
   const GemmDesc& d = batch.d[p];
-  const int t = bid - d.tile_begin;
-  if (t >= d.tiles_m * d.tiles_n) return;
-  int tr, tc;
   place_tile(d, t, tr, tc);
   const int m0 = tr * kFBM, n0 = tc * BN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1654,50 +1693,35 @@ __global__ __launch_bounds__(64 * kX6Waves, 2) void k_fwd_x6(GemmBatch batch) {
     offB[i] = (uint32_t)min(n0 + tid / TPR + RPP * i, N - 1) * (uint32_t)d.ldb * 4u;
   const int kq = 4 * (tid % TPR);
   float4 ga[NA], gb[NB];
-  auto zk = [&](float4 x, int k) {    // elements past K read the row's next columns: zeroed
-    x.x = k < K ? x.x : 0.f; x.y = k + 1 < K ? x.y : 0.f; x.z = k + 2 < K ? x.z : 0.f; x.w = k + 3 < K ? x.w : 0.f;
-    return x;
-  };
   auto gload = [&](int k0) {
     const int k = k0 + kq;
     const uint32_t ko = (uint32_t)(k < K ? k : 0) * 4u;
 #pragma unroll
-    for (int i = 0; i < NA; ++i) ga[i] = zk(buf_ld4(rA, offA[i] + ko), k);
+    for (int i = 0; i < NA; ++i) ga[i] = mask4(buf_ld4(rA, offA[i] + ko), k, K);
 #pragma unroll
-    for (int i = 0; i < NB; ++i) gb[i] = zk(buf_ld4(rB, offB[i] + ko), k);
+    for (int i = 0; i < NB; ++i) gb[i] = mask4(buf_ld4(rB, offB[i] + ko), k, K);
   };
   auto swrite = [&]() {
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
-      u2v h, m, l;
-      x6_split4(ga[i], h, m, l);
-      const int r = tid / TPR + RPP * i, c = cw(r, kq);
-      *reinterpret_cast<u2v*>(&sA[0][r][c]) = h;
-      *reinterpret_cast<u2v*>(&sA[1][r][c]) = m;
-      *reinterpret_cast<u2v*>(&sA[2][r][c]) = l;
+      const int r = tid / TPR + RPP * i, c = x6_swz(r, kq);
+      x6_store3(&sA[0][r][c], &sA[1][r][c], &sA[2][r][c], ga[i]);
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-      u2v h, m, l;
-      x6_split4(gb[i], h, m, l);
-      const int r = tid / TPR + RPP * i, c = cw(r, kq);
-      *reinterpret_cast<u2v*>(&sB[0][r][c]) = h;
-      *reinterpret_cast<u2v*>(&sB[1][r][c]) = m;
-      *reinterpret_cast<u2v*>(&sB[2][r][c]) = l;
+      const int r = tid / TPR + RPP * i, c = x6_swz(r, kq);
+      x6_store3(&sB[0][r][c], &sB[1][r][c], &sB[2][r][c], gb[i]);
     }
   };
   f4 acc[MI][NT];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   FwdEpi<NT, MI> ep;
   ep.load(d, n0 + wn, lane);
   gload(0);
   swrite();
   __syncthreads();
   const int nslab = (K + kX6K - 1) / kX6K;
-  const int kc = cw(lane & 15, 8 * (lane >> 4));   // (row blocks start at multiples of 16)
+  const int kc = x6_swz(lane & 15, 8 * (lane >> 4));   // (row blocks start at multiples of 16)
   for (int sl = 0; sl < nslab; ++sl) {
     if (sl + 1 < nslab) gload((sl + 1) * kX6K);
     // the A parts of every row block, then each B column block's parts just before its
@@ -1717,15 +1741,7 @@ __global__ __launch_bounds__(64 * kX6Waves, 2) void k_fwd_x6(GemmBatch batch) {
       const bf16x8 bm = *reinterpret_cast<const bf16x8*>(&sB[1][r][kc]);
       const bf16x8 bl = *reinterpret_cast<const bf16x8*>(&sB[2][r][kc]);
 #pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        f4 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bm, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bm, c, 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh, c, 0, 0, 0);
-      }
+      for (int i = 0; i < MI; ++i) x6_mfma(acc[i][j], ah[i], am[i], al[i], bh, bm, bl);
     }
     if (sl + 1 < nslab) {
       __syncthreads();   // every wave's fragment reads of this slab done
@@ -1787,14 +1803,9 @@ __global__ __launch_bounds__(1024, 1) void k_fwd16p(GemmBatch batch) {
   constexpr int APW = BM / 8 / NWV;                  // ... of them A pieces
   static_assert(NST >= 3 && PPW * NWV * 8 == BM + BN && APW * NWV * 8 == BM, "k_fwd16p geometry");
   __shared__ __attribute__((aligned(16))) unsigned char lds[NST * STAGE];
-  const int bid = blockIdx.x;
-  int p = 0;
-  for (int q = 1; q < batch.count; ++q)
-    if (bid >= batch.d[q].tile_begin) p = q;
+  int p, t, tr, tc;
+  if (!level_tile(batch, blockIdx.x, p, t)) return;
   const GemmDesc& d = batch.d[p];
-  const int t = bid - d.tile_begin;
-  if (t >= d.tiles_m * d.tiles_n) return;
-  int tr, tc;
   place_tile(d, t, tr, tc);
   const int m0 = tr * BM, n0 = tc * BN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1973,6 +1984,92 @@ __device__ __forceinline__ s4t lds_tr16(const __bf16* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s4t*)(p));
 }
+// one transposed 16x32 fragment: the lane's k row (k 0..3 of its group's 8) and the row 4 below
+__device__ __forceinline__ bf16x8 frag_tr16(const __bf16* row_lo, const __bf16* row_hi) {
+  const s4t lo = lds_tr16(row_lo);
+  const s4t hi = lds_tr16(row_hi);
+  const s8t v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// a split-K partial workgroup's work: K split `split` of the output tile at (m0, n0) of
+// descriptor p, the split's K range [kb, ke) in whole 64-deep units (a split may start
+// past K: an empty range).  false: a pad workgroup.
+struct DwTile { int split, p, m0, n0, kb, ke; };
+__device__ __forceinline__ bool dw_tile(const GemmBatch& batch, int ns, DwTile& w) {
+  const int tiles_tot = batch.total_tiles;
+  const int wk = dw_work_index(blockIdx.x, tiles_tot, ns);
+  if (wk < 0) return false;
+  int t;
+  if (!level_tile(batch, wk % tiles_tot, w.p, t)) return false;
+  const GemmDesc& d = batch.d[w.p];
+  w.split = wk / tiles_tot;
+  w.m0 = (t / d.tiles_n) * kDBM;
+  w.n0 = (t % d.tiles_n) * kDBN;
+  const int kc = ((d.K + ns - 1) / ns + kD16K - 1) / kD16K * kD16K;
+  w.kb = w.split * kc;
+  w.ke = min(d.K, w.kb + kc);
+  return true;
+}
+
+// the first column of a thread's 4-wide operand read at column c of an n-column operand:
+// a 4-aligned column <= the last one, so the read stays inside a row padded to a multiple
+// of 4; an operand narrower than 4 columns (the fc3 gradient dq, lda = 1) reads up to 3
+// floats past its last row: dw_split_plan's caller keeps that slack allocated (sacmi.hip:
+// dq).  (A per-load scalar fallback under a branch measured L6 74 -> 93 us: the guarded
+// loads drain the load queue.)
+__device__ __forceinline__ int dw_col4(int c, int n) { return min(c, (n - 1) & ~3); }
+
+// ride-along workgroup rb of a partial launch: the next update's sampling (one workgroup,
+// its table in the kernel's LDS block) or gather
+__device__ __forceinline__ void dw_ride(const RideAlong& ride, int rb, uint32_t* lds) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (ride.kind == 1) {
+    if (rb == 0) mt_sample_body(ride.mt, ride.tbl_log2, lds);
+  } else {
+    for (int b = rb * kDw16Waves + wave; b < ride.ga.B; b += ride.nblocks * kDw16Waves)
+      gather_row(ride.ga, b, lane, 64);
+  }
+}
+
+// partial `split` of descriptor p in the workspace
+__device__ __forceinline__ float* dw_partial(const GemmBatch& batch, int p, int split, int64_t ws_stride) {
+  int64_t off = 0;
+  for (int q = 0; q < p; ++q) off += (int64_t)batch.d[q].M * dw_ncols(batch.d[q]);
+  return batch.ws + (int64_t)split * ws_stride + off;
+}
+// a wave's 64 x 16 NJ accumulator block at (row0, col0) into the partial w ([M][nc])
+template <int NJ>
+__device__ __forceinline__ void dw_store_partial(float* w, int nc, const f4 (&acc)[4][NJ], int row0,
+                                                 int col0, int M, int N, int lane) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = row0 + i * 16 + (lane >> 4) * 4 + r;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int col = col0 + j * 16 + (lane & 15);
+        if (row < M && col < N) st_big(w + (int64_t)row * nc + col, acc[i][j][r]);
+      }
+    }
+}
+// the row-sum partial: each thread's sums over its staged k rows (columns 4 (t & 31) .. +3,
+// k rows t >> 5 + ...) through the scratch, then per column over the kDw16Krp threads
+// sharing it in fixed order, to column N of the partial
+__device__ __forceinline__ void dw_store_rowsum(float (&s_rs)[kDw16Krp][kDBM], const float (&rs4)[4],
+                                                float* w, int nc, int m0, int M, int N) {
+  const int tid = threadIdx.x, c4 = 4 * (tid & 31), kr0 = tid >> 5;
+  s_rs[kr0][c4] = rs4[0]; s_rs[kr0][c4 + 1] = rs4[1];
+  s_rs[kr0][c4 + 2] = rs4[2]; s_rs[kr0][c4 + 3] = rs4[3];
+  __syncthreads();
+  if (tid < kDBM && m0 + tid < M) {
+#pragma clang fp contract(off)
+    float v = s_rs[0][tid];
+    for (int g = 1; g < kDw16Krp; ++g) v += s_rs[g][tid];
+    st_big(w + (int64_t)(m0 + tid) * nc + N, v);
+  }
+}
 
 // X16 (act16): the B operand (X: activations / minibatch inputs) is bf16
 template <bool X16 = false>
@@ -1987,31 +2084,16 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part16(GemmBatch batc
   auto& s_rs = *reinterpret_cast<float (*)[kDw16Krp][kDBM]>(lds_raw + 2 * kDw16OpBytes);
   constexpr int NWV = kDw16Waves, WC = NWV / 2, NJ = kDBN / WC / 16;   // 2 x WC waves of 64 x (128 / WC)
   constexpr int KRP = kDw16Krp, NI = kD16K / KRP;                       // staging: KRP k rows a pass
-  const int tiles_tot = batch.total_tiles;
-  const int nwg = dw_grid_tiles(tiles_tot, ns);
-  if ((int)blockIdx.x >= nwg) {   // ride-along: the next update's sampling or gather
-    const int rb = blockIdx.x - nwg, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (batch.ride.kind == 1) {
-      if (rb == 0) mt_sample_body(batch.ride.mt, batch.ride.tbl_log2, reinterpret_cast<uint32_t*>(lds_raw));
-    } else {
-      for (int b = rb * NWV + wave; b < batch.ride.ga.B; b += batch.ride.nblocks * NWV)
-        gather_row(batch.ride.ga, b, lane, 64);
-    }
+  const int nwg = dw_grid_tiles(batch.total_tiles, ns);
+  if ((int)blockIdx.x >= nwg) {
+    dw_ride(batch.ride, blockIdx.x - nwg, reinterpret_cast<uint32_t*>(lds_raw));
     return;
   }
-  const int wk = dw_work_index(blockIdx.x, tiles_tot, ns);
-  if (wk < 0) return;
-  const int split = wk / tiles_tot, bid = wk % tiles_tot;
-  int p = 0;
-  for (int q = 1; q < batch.count; ++q)
-    if (bid >= batch.d[q].tile_begin) p = q;
-  const GemmDesc& d = batch.d[p];
-  const int t = bid - d.tile_begin;
-  if (t >= d.tiles_m * d.tiles_n) return;
-  const int m0 = (t / d.tiles_n) * kDBM, n0 = (t % d.tiles_n) * kDBN;
+  DwTile w;
+  if (!dw_tile(batch, ns, w)) return;
+  const GemmDesc& d = batch.d[w.p];
+  const int m0 = w.m0, n0 = w.n0, kb = w.kb, ke = w.ke;
   const int M = d.M, N = d.N, K = d.K;
-  const int kc = ((K + ns - 1) / ns + kD16K - 1) / kD16K * kD16K;
-  const int kb = split * kc, ke = min(K, kb + kc);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave / WC) * 64, wn = (wave % WC) * (kDBN / WC);
   // staging: thread t moves k rows (t >> 5) + KRP i (i < NI), columns 4 (t & 31) .. +3
@@ -2019,12 +2101,7 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part16(GemmBatch batc
   const rsrc_t rA = make_rsrc(d.A, 0x7fffffffu), rB = make_rsrc(d.B, 0x7fffffffu);
   const rsrc_t rS = make_rsrc(d.a_ksc ? d.a_ksc : d.A, d.a_ksc ? (uint32_t)K * 4u : 0u);
   const bool has_ksc = d.a_ksc != nullptr;
-  // 4-wide operand reads start at a 4-aligned column <= the last one, so they stay inside
-  // a row padded to a multiple of 4; an operand narrower than 4 columns (the fc3 gradient
-  // dq, lda = 1) reads up to 3 floats past its last row: dw_split_plan's caller keeps
-  // that slack allocated (sacmi.hip: dq).  (A per-load scalar fallback under a branch
-  // measured L6 74 -> 93 us: the guarded loads drain the load queue.)
-  const int ma = min(m0 + c4, (M - 1) & ~3), nb = min(n0 + c4, (N - 1) & ~3);
+  const int ma = dw_col4(m0 + c4, M), nb = dw_col4(n0 + c4, N);
   const bool want_rs = d.rs_col >= 0 && n0 == 0;
   float4 ga[NI], gb[X16 ? 1 : NI];
   uint2 gbh[X16 ? NI : 1];
@@ -2035,24 +2112,12 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part16(GemmBatch batc
       const int k = k0 + kr0 + KRP * i;
       const bool kin = k < ke;
       const uint32_t kk = (uint32_t)(kin ? k : 0);   // row 0 always exists (a split may start past K)
-      const uint32_t ea = kk * (uint32_t)d.lda + (uint32_t)ma;
-      float4 x = buf_ld4(rA, ea * 4u);
+      const float4 x = buf_ld4(rA, (kk * (uint32_t)d.lda + (uint32_t)ma) * 4u);
       const float f = has_ksc ? buf_ld(rS, kk * 4u) : 1.f;
       // columns past M / N (and rows past this split's K range) contribute zero
-      x.x = kin && m0 + c4 < M ? x.x * f : 0.f;     x.y = kin && m0 + c4 + 1 < M ? x.y * f : 0.f;
-      x.z = kin && m0 + c4 + 2 < M ? x.z * f : 0.f; x.w = kin && m0 + c4 + 3 < M ? x.w * f : 0.f;
-      ga[i] = x;
-      if constexpr (X16) {
-        uint2 h = buf_ld2(rB, (kk * (uint32_t)d.ldb + (uint32_t)nb) * 2u);
-        h.x = (kin && n0 + c4 < N ? h.x & 0xffffu : 0u) | (kin && n0 + c4 + 1 < N ? h.x & 0xffff0000u : 0u);
-        h.y = (kin && n0 + c4 + 2 < N ? h.y & 0xffffu : 0u) | (kin && n0 + c4 + 3 < N ? h.y & 0xffff0000u : 0u);
-        gbh[i] = h;
-      } else {
-        float4 y = buf_ld4(rB, (kk * (uint32_t)d.ldb + (uint32_t)nb) * 4u);
-        y.x = kin && n0 + c4 < N ? y.x : 0.f;         y.y = kin && n0 + c4 + 1 < N ? y.y : 0.f;
-        y.z = kin && n0 + c4 + 2 < N ? y.z : 0.f;     y.w = kin && n0 + c4 + 3 < N ? y.w : 0.f;
-        gb[i] = y;
-      }
+      ga[i] = mask4(make_float4(x.x * f, x.y * f, x.z * f, x.w * f), m0 + c4, M, kin);
+      if constexpr (X16) gbh[i] = mask4h(buf_ld2(rB, (kk * (uint32_t)d.ldb + (uint32_t)nb) * 2u), n0 + c4, N, kin);
+      else gb[i] = mask4(buf_ld4(rB, (kk * (uint32_t)d.ldb + (uint32_t)nb) * 4u), n0 + c4, N, kin);
     }
   };
   auto swrite = [&](int buf, bool fresh) {   // fresh: a slab not staged before
@@ -2071,10 +2136,7 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part16(GemmBatch batc
     }
   };
   f4 acc[4][NJ];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   const int nslab = (ke - kb + kD16K - 1) / kD16K;
   // transposed-read lane roles: group g = lane >> 4 takes k 8g..8g+7; lane 4q+p of the
   // group addresses k row q (+4 for the second half), columns 4p..4p+3 of a 16-column block
@@ -2090,19 +2152,11 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part16(GemmBatch batc
       const int kr = kk * 32 + 8 * tg + tq;
       bf16x8 a[4], b[NJ];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const s4t lo = lds_tr16(&sA[cur][kr][wm + i * 16 + 4 * tp]);
-        const s4t hi = lds_tr16(&sA[cur][kr + 4][wm + i * 16 + 4 * tp]);
-        const s8t v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        a[i] = __builtin_bit_cast(bf16x8, v);
-      }
+      for (int i = 0; i < 4; ++i)
+        a[i] = frag_tr16(&sA[cur][kr][wm + i * 16 + 4 * tp], &sA[cur][kr + 4][wm + i * 16 + 4 * tp]);
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const s4t lo = lds_tr16(&sB[cur][kr][wn + j * 16 + 4 * tp]);
-        const s4t hi = lds_tr16(&sB[cur][kr + 4][wn + j * 16 + 4 * tp]);
-        const s8t v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        b[j] = __builtin_bit_cast(bf16x8, v);
-      }
+      for (int j = 0; j < NJ; ++j)
+        b[j] = frag_tr16(&sB[cur][kr][wn + j * 16 + 4 * tp], &sB[cur][kr + 4][wn + j * 16 + 4 * tp]);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -2113,32 +2167,10 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part16(GemmBatch batc
     __syncthreads();
   }
   // partial tile (+ row-sum partial) to the workspace
-  int64_t off = 0;
-  for (int q = 0; q < p; ++q) off += (int64_t)batch.d[q].M * dw_ncols(batch.d[q]);
-  float* w = batch.ws + (int64_t)split * ws_stride + off;
+  float* const ws = dw_partial(batch, w.p, w.split, ws_stride);
   const int nc = dw_ncols(d);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int col = n0 + wn + j * 16 + (lane & 15);
-        if (row < M && col < N) st_big(w + (int64_t)row * nc + col, acc[i][j][r]);
-      }
-    }
-  if (want_rs) {
-    s_rs[kr0][c4] = rs4[0]; s_rs[kr0][c4 + 1] = rs4[1];
-    s_rs[kr0][c4 + 2] = rs4[2]; s_rs[kr0][c4 + 3] = rs4[3];
-    __syncthreads();
-    if (tid < kDBM && m0 + tid < M) {
-#pragma clang fp contract(off)
-      float v = s_rs[0][tid];
-      for (int g = 1; g < KRP; ++g) v += s_rs[g][tid];
-      st_big(w + (int64_t)(m0 + tid) * nc + N, v);
-    }
-  }
+  dw_store_partial(ws, nc, acc, m0 + wm, n0 + wn, M, N, lane);
+  if (want_rs) dw_store_rowsum(s_rs, rs4, ws, nc, m0, M, N);
 }
 
 // fp32 mode, batch-4096 class: the deep-K weight-gradient partials on bf16 MFMA with the
@@ -2161,39 +2193,23 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part_x6(GemmBatch bat
   constexpr int NWV = kDw16Waves, WC = NWV / 2, NJ = kDBN / WC / 16;   // 2 x WC waves of 64 x (128 / WC)
   constexpr int KRP = kDw16Krp, NI = kDX6K / KRP;                      // staging: KRP k rows a pass
   static_assert(NI >= 1, "k_dw_part_x6 staging");
-  const int tiles_tot = batch.total_tiles;
-  const int nwg = dw_grid_tiles(tiles_tot, ns);
-  if ((int)blockIdx.x >= nwg) {   // ride-along: the next update's sampling or gather
-    const int rb = blockIdx.x - nwg, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (batch.ride.kind == 1) {
-      if (rb == 0) mt_sample_body(batch.ride.mt, batch.ride.tbl_log2, reinterpret_cast<uint32_t*>(lds_raw));
-    } else {
-      for (int b = rb * NWV + wave; b < batch.ride.ga.B; b += batch.ride.nblocks * NWV)
-        gather_row(batch.ride.ga, b, lane, 64);
-    }
+  const int nwg = dw_grid_tiles(batch.total_tiles, ns);
+  if ((int)blockIdx.x >= nwg) {
+    dw_ride(batch.ride, blockIdx.x - nwg, reinterpret_cast<uint32_t*>(lds_raw));
     return;
   }
-  const int wk = dw_work_index(blockIdx.x, tiles_tot, ns);
-  if (wk < 0) return;
-  const int split = wk / tiles_tot, bid = wk % tiles_tot;
-  int p = 0;
-  for (int q = 1; q < batch.count; ++q)
-    if (bid >= batch.d[q].tile_begin) p = q;
-  const GemmDesc& d = batch.d[p];
-  const int t = bid - d.tile_begin;
-  if (t >= d.tiles_m * d.tiles_n) return;
-  const int m0 = (t / d.tiles_n) * kDBM, n0 = (t % d.tiles_n) * kDBN;
+  DwTile w;
+  if (!dw_tile(batch, ns, w)) return;
+  const GemmDesc& d = batch.d[w.p];
+  const int m0 = w.m0, n0 = w.n0, kb = w.kb, ke = w.ke;
   const int M = d.M, N = d.N, K = d.K;
-  // the split's K range in whole 64-deep units (k_dw_part16's ranges: the same partition)
-  const int kc = ((K + ns - 1) / ns + kD16K - 1) / kD16K * kD16K;
-  const int kb = split * kc, ke = min(K, kb + kc);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave / WC) * 64, wn = (wave % WC) * (kDBN / WC);
   const int c4 = 4 * (tid & 31), kr0 = tid >> 5;
   const rsrc_t rA = make_rsrc(d.A, 0x7fffffffu), rB = make_rsrc(d.B, 0x7fffffffu);
   const rsrc_t rS = make_rsrc(d.a_ksc ? d.a_ksc : d.A, d.a_ksc ? (uint32_t)K * 4u : 0u);
   const bool has_ksc = d.a_ksc != nullptr;
-  const int ma = min(m0 + c4, (M - 1) & ~3), nb = min(n0 + c4, (N - 1) & ~3);
+  const int ma = dw_col4(m0 + c4, M), nb = dw_col4(n0 + c4, N);
   const bool want_rs = d.rs_col >= 0 && n0 == 0;
   float4 ga[NI], gb[NI];
   float rs4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -2203,30 +2219,18 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part_x6(GemmBatch bat
       const int k = k0 + kr0 + KRP * i;
       const bool kin = k < ke;
       const uint32_t kk = (uint32_t)(kin ? k : 0);
-      float4 x = buf_ld4(rA, (kk * (uint32_t)d.lda + (uint32_t)ma) * 4u);
+      const float4 x = buf_ld4(rA, (kk * (uint32_t)d.lda + (uint32_t)ma) * 4u);
       const float f = has_ksc ? buf_ld(rS, kk * 4u) : 1.f;
-      x.x = kin && m0 + c4 < M ? x.x * f : 0.f;     x.y = kin && m0 + c4 + 1 < M ? x.y * f : 0.f;
-      x.z = kin && m0 + c4 + 2 < M ? x.z * f : 0.f; x.w = kin && m0 + c4 + 3 < M ? x.w * f : 0.f;
-      ga[i] = x;
-      float4 y = buf_ld4(rB, (kk * (uint32_t)d.ldb + (uint32_t)nb) * 4u);
-      y.x = kin && n0 + c4 < N ? y.x : 0.f;         y.y = kin && n0 + c4 + 1 < N ? y.y : 0.f;
-      y.z = kin && n0 + c4 + 2 < N ? y.z : 0.f;     y.w = kin && n0 + c4 + 3 < N ? y.w : 0.f;
-      gb[i] = y;
+      ga[i] = mask4(make_float4(x.x * f, x.y * f, x.z * f, x.w * f), m0 + c4, M, kin);
+      gb[i] = mask4(buf_ld4(rB, (kk * (uint32_t)d.ldb + (uint32_t)nb) * 4u), n0 + c4, N, kin);
     }
   };
   auto swrite = [&]() {
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-      const int r = kr0 + KRP * i;
-      u2v h, m, l;
-      x6_split4(ga[i], h, m, l);
-      *reinterpret_cast<u2v*>(sAp + 0 * PL + r * LDR + c4) = h;
-      *reinterpret_cast<u2v*>(sAp + 1 * PL + r * LDR + c4) = m;
-      *reinterpret_cast<u2v*>(sAp + 2 * PL + r * LDR + c4) = l;
-      x6_split4(gb[i], h, m, l);
-      *reinterpret_cast<u2v*>(sBp + 0 * PL + r * LDR + c4) = h;
-      *reinterpret_cast<u2v*>(sBp + 1 * PL + r * LDR + c4) = m;
-      *reinterpret_cast<u2v*>(sBp + 2 * PL + r * LDR + c4) = l;
+      const int e = (kr0 + KRP * i) * LDR + c4;
+      x6_store3(sAp + e, sAp + PL + e, sAp + 2 * PL + e, ga[i]);
+      x6_store3(sBp + e, sBp + PL + e, sBp + 2 * PL + e, gb[i]);
     }
     if (want_rs) {
 #pragma clang fp contract(off)
@@ -2237,18 +2241,12 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part_x6(GemmBatch bat
     }
   };
   f4 acc[4][NJ];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   const int nslab = (ke - kb + kDX6K - 1) / kDX6K;
   const int tq = (lane & 15) >> 2, tp = lane & 3, tg = lane >> 4;
   const int kr = 8 * tg + tq;
   auto frag = [&](const __bf16* plane, int col) {   // transposed 16x32 fragment at column col
-    const s4t lo = lds_tr16(plane + kr * LDR + col);
-    const s4t hi = lds_tr16(plane + (kr + 4) * LDR + col);
-    const s8t v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    return __builtin_bit_cast(bf16x8, v);
+    return frag_tr16(plane + kr * LDR + col, plane + (kr + 4) * LDR + col);
   };
   if (nslab > 0) {
     gload(kb);
@@ -2270,15 +2268,7 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part_x6(GemmBatch bat
       const int col = wn + j * 16 + 4 * tp;
       const bf16x8 bh = frag(sBp, col), bm = frag(sBp + PL, col), bl = frag(sBp + 2 * PL, col);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        f4 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bm, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bm, c, 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh, c, 0, 0, 0);
-      }
+      for (int i = 0; i < 4; ++i) x6_mfma(acc[i][j], ah[i], am[i], al[i], bh, bm, bl);
     }
     if (sl + 1 < nslab) {
       __syncthreads();   // every wave's fragment reads of this slab done
@@ -2287,32 +2277,12 @@ __global__ __launch_bounds__(64 * kDw16Waves, 2) void k_dw_part_x6(GemmBatch bat
     }
   }
   // partial tile (+ row-sum partial) to the workspace
-  int64_t off = 0;
-  for (int q = 0; q < p; ++q) off += (int64_t)batch.d[q].M * dw_ncols(batch.d[q]);
-  float* w = batch.ws + (int64_t)split * ws_stride + off;
+  float* const ws = dw_partial(batch, w.p, w.split, ws_stride);
   const int nc = dw_ncols(d);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int col = n0 + wn + j * 16 + (lane & 15);
-        if (row < M && col < N) st_big(w + (int64_t)row * nc + col, acc[i][j][r]);
-      }
-    }
+  dw_store_partial(ws, nc, acc, m0 + wm, n0 + wn, M, N, lane);
   if (want_rs) {
-    __syncthreads();
-    s_rs[kr0][c4] = rs4[0]; s_rs[kr0][c4 + 1] = rs4[1];
-    s_rs[kr0][c4 + 2] = rs4[2]; s_rs[kr0][c4 + 3] = rs4[3];
-    __syncthreads();
-    if (tid < kDBM && m0 + tid < M) {
-#pragma clang fp contract(off)
-      float v = s_rs[0][tid];
-      for (int g = 1; g < KRP; ++g) v += s_rs[g][tid];
-      st_big(w + (int64_t)(m0 + tid) * nc + N, v);
-    }
+    __syncthreads();   // (this kernel's own barrier ahead of the scratch write; k_dw_part16 has none)
+    dw_store_rowsum(s_rs, rs4, ws, nc, m0, M, N);
   }
 }
 
@@ -2331,6 +2301,66 @@ constexpr int kXBM = 64, kXBN = 128, kXBK = 64;
 // ACT16 (act16 updates): the ReLU-mask source (aux) is bf16, and so is A where it is the
 // activation whose sign the transform reads (AX); the plain levels' A is a gradient, fp32
 constexpr int kAxWaves = 8;   // waves per k_axk16 workgroup: 2 x 4 of 32x32 sub-tiles
+
+// ride-along workgroup rb of a dh launch: the next update's gather, a row a wave
+// (one row of 3 float4 per lane: the branch's registers stay under the tiles' 128 —
+// two rows a wave took k_axk16 to 131 VGPRs, one 8-wave workgroup per CU)
+__device__ __forceinline__ void dh_ride(const RideAlong& ride, int rb) {
+  const int wv = rb * kAxWaves + (int)(threadIdx.x >> 6), nwv = ride.nblocks * kAxWaves;
+  for (int b0 = wv; b0 < ride.ga.B; b0 += nwv)
+    gather_rows_wave<1, 3>(ride.ga, b0, nwv, threadIdx.x & 63);
+}
+
+// the A transform of the row-prologue levels: u = [h2 > 0] w3 (exact fp32 values: w3 or 0)
+__device__ __forceinline__ float4 dh_u4(float4 a, float4 w) {
+  return make_float4(a.x > 0.f ? w.x : 0.f, a.y > 0.f ? w.y : 0.f, a.z > 0.f ? w.z : 0.f, a.w > 0.f ? w.w : 0.f);
+}
+
+// the ReLU-mask source (aux; ACT16: bf16) of a wave's 32 x 16 NJ block at (row0, col0), in
+// the accumulator layout; elements outside M x N read an out-of-range offset (0)
+template <bool ACT16, int NJ>
+__device__ __forceinline__ void dh_mask_load(const GemmDesc& d, float (&hm)[2][NJ][4], int row0,
+                                             int col0, int lane) {
+  constexpr uint32_t xe = ACT16 ? 2u : 4u;   // mask-source element bytes
+  const int M = d.M, N = d.N;
+  const rsrc_t rX = make_rsrc(d.aux, (uint32_t)(((size_t)(M - 1) * d.ldaux + N) * xe));
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = row0 + i * 16 + (lane >> 4) * 4 + r;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int col = col0 + j * 16 + (lane & 15);
+        const uint32_t off = row < M && col < N ? (uint32_t)(row * d.ldaux + col) * xe : 0xfffffff0u;
+        hm[i][j][r] = ACT16 ? bf16_lo(buf_ld_u16(rX, off)) : buf_ld(rX, off);
+      }
+    }
+}
+
+// dh epilogue of that block (tile rows m0.., the wave's at wm): coefficient, ReLU-backward
+// mask, store (k_gemm's op order)
+template <bool AX, int NJ>
+__device__ __forceinline__ void dh_epilogue(const GemmDesc& d, const f4 (&acc)[2][NJ],
+                                            const float (&hm)[2][NJ][4], const float (&s_coef)[2][kXBM],
+                                            int m0, int wm, int col0, int lane) {
+  const int M = d.M, N = d.N;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int lr = wm + i * 16 + (lane >> 4) * 4 + r, row = m0 + lr;
+      const float cf = AX ? s_coef[d.ax_slot][lr] : 1.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int col = col0 + j * 16 + (lane & 15);
+        float v = acc[i][j][r];
+        if (AX) v *= cf;
+        v = hm[i][j][r] > 0.f ? v : 0.f;
+        if (row < M && col < N) st_big(d.C + (size_t)row * d.ldc + col, v);
+      }
+    }
+}
 template <bool AX, bool BH = false, bool ACT16 = false>
 __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk16(GemmBatch batch) {
   const TlMark tl_mark(batch.tl, TL_AXK16);
@@ -2343,21 +2373,13 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk16(GemmBatch batch) {
   constexpr int ARP = NTH / 16, NAI = kXBM / ARP;   // A staging: rows a pass, passes
   constexpr int BKP = NTH / 32, NBI = kXBK / BKP;   // B staging: k rows a pass, passes
   const int bid = blockIdx.x;
-  if (bid >= batch.total_tiles) {   // ride-along: the next update's gather, a row a wave
-    // (one row of 3 float4 per lane: the branch's registers stay under the tiles' 128 —
-    // two rows a wave took the kernel to 131 VGPRs, one 8-wave workgroup per CU)
-    const int wv = (bid - batch.total_tiles) * NWV + (int)(threadIdx.x >> 6), nwv = batch.ride.nblocks * NWV;
-    for (int b0 = wv; b0 < batch.ride.ga.B; b0 += nwv)
-      gather_rows_wave<1, 3>(batch.ride.ga, b0, nwv, threadIdx.x & 63);
+  if (bid >= batch.total_tiles) {
+    dh_ride(batch.ride, bid - batch.total_tiles);
     return;
   }
-  int p = 0;
-  for (int q = 1; q < batch.count; ++q)
-    if (bid >= batch.d[q].tile_begin) p = q;
+  int p, t, tr, tc;
+  if (!level_tile(batch, bid, p, t)) return;
   const GemmDesc& d = batch.d[p];
-  const int t = bid - d.tile_begin;
-  if (t >= d.tiles_m * d.tiles_n) return;
-  int tr, tc;
   place_tile(d, t, tr, tc);
   const int m0 = tr * kXBM, n0 = tc * kXBN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2420,17 +2442,8 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk16(GemmBatch batch) {
       const int kb = k0 + kr0 + BKP * i;
       const bool kin = kb < K;
       const uint32_t e = (uint32_t)(kin ? kb : 0) * (uint32_t)d.ldb + (uint32_t)nb;
-      if constexpr (BH) {
-        uint2 h = buf_ld2(rBh, e * 2u);
-        h.x = (kin && n0 + c4 < N ? h.x & 0xffffu : 0u) | (kin && n0 + c4 + 1 < N ? h.x & 0xffff0000u : 0u);
-        h.y = (kin && n0 + c4 + 2 < N ? h.y & 0xffffu : 0u) | (kin && n0 + c4 + 3 < N ? h.y & 0xffff0000u : 0u);
-        gh[i] = h;
-      } else {
-        float4 y = buf_ld4(rB, e * 4u);
-        y.x = kin && n0 + c4 < N ? y.x : 0.f;         y.y = kin && n0 + c4 + 1 < N ? y.y : 0.f;
-        y.z = kin && n0 + c4 + 2 < N ? y.z : 0.f;     y.w = kin && n0 + c4 + 3 < N ? y.w : 0.f;
-        gb[i] = y;
-      }
+      if constexpr (BH) gh[i] = mask4h(buf_ld2(rBh, e * 2u), n0 + c4, N, kin);
+      else gb[i] = mask4(buf_ld4(rB, e * 4u), n0 + c4, N, kin);
     }
   };
   auto swrite = [&](int buf, int k0, bool fresh) {
@@ -2438,15 +2451,9 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk16(GemmBatch batch) {
     const bool k_in = k0 + kXBK <= K;
 #pragma unroll
     for (int i = 0; i < NAI; ++i) {
-      // u = [h2 > 0] w3 (exact fp32 values: w3 or 0), rounded to bf16 for the MFMAs
-      const float4 a = ga[i];
-      const float4 u = k_in ? (AX ? make_float4(a.x > 0.f ? gw.x : 0.f, a.y > 0.f ? gw.y : 0.f,
-                                                a.z > 0.f ? gw.z : 0.f, a.w > 0.f ? gw.w : 0.f)
-                                  : a)
-                     : AX ? make_float4(a.x > 0.f && k < K ? gw.x : 0.f, a.y > 0.f && k + 1 < K ? gw.y : 0.f,
-                                        a.z > 0.f && k + 2 < K ? gw.z : 0.f, a.w > 0.f && k + 3 < K ? gw.w : 0.f)
-                          : make_float4(k < K ? a.x : 0.f, k + 1 < K ? a.y : 0.f,
-                                        k + 2 < K ? a.z : 0.f, k + 3 < K ? a.w : 0.f);
+      // the A rows (AX: transformed), rounded to bf16 for the MFMAs; k past K zeroed
+      const float4 a = AX ? dh_u4(ga[i], gw) : ga[i];
+      const float4 u = k_in ? a : mask4(a, k, K);
       const int r = (tid >> 4) + ARP * i;
       *reinterpret_cast<u2v*>(&sA[buf][r][kq]) = pack_bf16x4(u);
       if (fresh) {
@@ -2462,31 +2469,13 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk16(GemmBatch batch) {
     }
   };
   f4 acc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   gload(0);
   // the row prologue's loads and the ReLU-mask source, behind the first slab's loads
   RowsRegs rows_x{};
   if constexpr (AX) rows_load<kXBM, NTH>(batch.rows, d, m0, rows_x);
   float hm[2][NJ][4];
-  {
-    constexpr uint32_t xe = ACT16 ? 2u : 4u;   // mask-source element bytes
-    const rsrc_t rX = make_rsrc(d.aux, (uint32_t)(((size_t)(M - 1) * d.ldaux + N) * xe));
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int col = n0 + wn + j * 16 + (lane & 15);
-          const uint32_t off = row < M && col < N ? (uint32_t)(row * d.ldaux + col) * xe : 0xfffffff0u;
-          hm[i][j][r] = ACT16 ? bf16_lo(buf_ld_u16(rX, off)) : buf_ld(rX, off);
-        }
-      }
-  }
+  dh_mask_load<ACT16>(d, hm, m0 + wm, n0 + wn, lane);
   swrite(0, 0, store_a);
   __syncthreads();
   const int nslab = (K + kXBK - 1) / kXBK;
@@ -2502,12 +2491,8 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk16(GemmBatch batch) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const bf16x8*>(&sA[cur][wm + i * 16 + (lane & 15)][kc]);
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const s4t lo = lds_tr16(&sB[cur][kc + tq][wn + j * 16 + 4 * tp]);
-        const s4t hi = lds_tr16(&sB[cur][kc + tq + 4][wn + j * 16 + 4 * tp]);
-        const s8t v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        b[j] = __builtin_bit_cast(bf16x8, v);
-      }
+      for (int j = 0; j < NJ; ++j)
+        b[j] = frag_tr16(&sB[cur][kc + tq][wn + j * 16 + 4 * tp], &sB[cur][kc + tq + 4][wn + j * 16 + 4 * tp]);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -2519,22 +2504,7 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk16(GemmBatch batch) {
   }
   const bool writer = p == 0 && n0 == 0;
   if constexpr (AX) rows_finish<kXBM, NTH>(batch.rows, d, m0, writer, bid == 0, rows_x, s_q, s_coef, s_l);
-  // epilogue: coefficient, ReLU-backward mask, store (k_gemm's op order)
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int lr = wm + i * 16 + (lane >> 4) * 4 + r, row = m0 + lr;
-      const float cf = AX ? s_coef[d.ax_slot][lr] : 1.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int col = n0 + wn + j * 16 + (lane & 15);
-        float v = acc[i][j][r];
-        if (AX) v *= cf;
-        v = hm[i][j][r] > 0.f ? v : 0.f;
-        if (row < M && col < N) st_big(d.C + (size_t)row * d.ldc + col, v);
-      }
-    }
+  dh_epilogue<AX>(d, acc, hm, s_coef, m0, wm, n0 + wn, lane);
   if constexpr (AX) rows_loss<kXBM>(batch.rows, m0, writer, s_l);
 }
 
@@ -2551,9 +2521,7 @@ constexpr int kXX6K = 32;
 template <bool AX, int BN = kXBN>
 __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk_x6(GemmBatch batch) {
   const TlMark tl_mark(batch.tl, TL_AXK_X6);
-  // [row][k] bf16, 64-B rows with k_fwd_x6's chunk swizzle (profiles/r06/x6_swizzle_ab)
-  constexpr int LDA_ = kXX6K;
-  auto cw = [](int r, int k) { return (((k >> 3) ^ ((r >> 2) & 2)) << 3) | (k & 7); };
+  constexpr int LDA_ = kXX6K;           // [row][k] bf16, 64-B rows, chunks swizzled (x6_swz)
   constexpr int LDB_ = BN + 8;          // [k][n] bf16
   __shared__ __attribute__((aligned(16))) __bf16 sA[3][kXBM][LDA_];
   __shared__ __attribute__((aligned(16))) __bf16 sB[3][kXX6K][LDB_];
@@ -2563,19 +2531,13 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk_x6(GemmBatch batch) {
   constexpr int TPRB = BN / 4, BKP = NTH / TPRB, NBI = kXX6K / BKP;     // B staging
   static_assert(NAI >= 1 && NBI >= 1 && NJ >= 1, "k_axk_x6 staging");
   const int bid = blockIdx.x;
-  if (bid >= batch.total_tiles) {   // ride-along: the next update's gather, a row a wave
-    const int wv = (bid - batch.total_tiles) * NWV + (int)(threadIdx.x >> 6), nwv = batch.ride.nblocks * NWV;
-    for (int b0 = wv; b0 < batch.ride.ga.B; b0 += nwv)
-      gather_rows_wave<1, 3>(batch.ride.ga, b0, nwv, threadIdx.x & 63);
+  if (bid >= batch.total_tiles) {
+    dh_ride(batch.ride, bid - batch.total_tiles);
     return;
   }
-  int p = 0;
-  for (int q = 1; q < batch.count; ++q)
-    if (bid >= batch.d[q].tile_begin) p = q;
+  int p, t, tr, tc;
+  if (!level_tile(batch, bid, p, t)) return;
   const GemmDesc& d = batch.d[p];
-  const int t = bid - d.tile_begin;
-  if (t >= d.tiles_m * d.tiles_n) return;
-  int tr, tc;
   place_tile(d, t, tr, tc);
   const int m0 = tr * kXBM, n0 = tc * BN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2605,28 +2567,18 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk_x6(GemmBatch batch) {
     for (int i = 0; i < NBI; ++i) {
       const int kb = k0 + kr0 + BKP * i;
       const bool kin = kb < K;
-      float4 y = buf_ld4(rB, ((uint32_t)(kin ? kb : 0) * (uint32_t)d.ldb + (uint32_t)nb) * 4u);
-      y.x = kin && n0 + c4 < N ? y.x : 0.f;         y.y = kin && n0 + c4 + 1 < N ? y.y : 0.f;
-      y.z = kin && n0 + c4 + 2 < N ? y.z : 0.f;     y.w = kin && n0 + c4 + 3 < N ? y.w : 0.f;
-      gb[i] = y;
+      gb[i] = mask4(buf_ld4(rB, ((uint32_t)(kin ? kb : 0) * (uint32_t)d.ldb + (uint32_t)nb) * 4u),
+                    n0 + c4, N, kin);
     }
   };
   auto swrite = [&](int k0, bool fresh) {
     const int k = k0 + kq;
 #pragma unroll
     for (int i = 0; i < NAI; ++i) {
-      // u = [h2 > 0] w3 (exact fp32 values: w3 or 0)
-      const float4 a = ga[i];
-      const float4 u = AX ? make_float4(a.x > 0.f && k < K ? gw.x : 0.f, a.y > 0.f && k + 1 < K ? gw.y : 0.f,
-                                        a.z > 0.f && k + 2 < K ? gw.z : 0.f, a.w > 0.f && k + 3 < K ? gw.w : 0.f)
-                          : make_float4(k < K ? a.x : 0.f, k + 1 < K ? a.y : 0.f,
-                                        k + 2 < K ? a.z : 0.f, k + 3 < K ? a.w : 0.f);
-      const int r = tid / TPRA + ARP * i;
-      u2v h, m, l;
-      x6_split4(u, h, m, l);
-      *reinterpret_cast<u2v*>(&sA[0][r][cw(r, kq)]) = h;
-      *reinterpret_cast<u2v*>(&sA[1][r][cw(r, kq)]) = m;
-      *reinterpret_cast<u2v*>(&sA[2][r][cw(r, kq)]) = l;
+      // the A rows (AX: transformed), k past K zeroed
+      const float4 u = mask4(AX ? dh_u4(ga[i], gw) : ga[i], k, K);
+      const int r = tid / TPRA + ARP * i, c = x6_swz(r, kq);
+      x6_store3(&sA[0][r][c], &sA[1][r][c], &sA[2][r][c], u);
       if (fresh) {
         const int rr = m0 + r;
         buf_st4(rAx, (rr < M && k < K) ? (uint32_t)(rr * d.ax_ld + k) * 4u : 0xfffffff0u,
@@ -2635,42 +2587,23 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk_x6(GemmBatch batch) {
     }
 #pragma unroll
     for (int i = 0; i < NBI; ++i) {
-      u2v h, m, l;
-      x6_split4(gb[i], h, m, l);
-      *reinterpret_cast<u2v*>(&sB[0][kr0 + BKP * i][c4]) = h;
-      *reinterpret_cast<u2v*>(&sB[1][kr0 + BKP * i][c4]) = m;
-      *reinterpret_cast<u2v*>(&sB[2][kr0 + BKP * i][c4]) = l;
+      const int r = kr0 + BKP * i;
+      x6_store3(&sB[0][r][c4], &sB[1][r][c4], &sB[2][r][c4], gb[i]);
     }
   };
   f4 acc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   gload(0);
   // the row prologue's loads and the ReLU-mask source, behind the first slab's loads
   RowsRegs rows_x{};
   if constexpr (AX) rows_load<kXBM, NTH>(batch.rows, d, m0, rows_x);
   float hm[2][NJ][4];
-  {
-    const rsrc_t rX = make_rsrc(d.aux, (uint32_t)(((size_t)(M - 1) * d.ldaux + N) * 4u));
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int col = n0 + wn + j * 16 + (lane & 15);
-          hm[i][j][r] = buf_ld(rX, row < M && col < N ? (uint32_t)(row * d.ldaux + col) * 4u : 0xfffffff0u);
-        }
-      }
-  }
+  dh_mask_load<false>(d, hm, m0 + wm, n0 + wn, lane);
   swrite(0, store_a);
   __syncthreads();
   const int nslab = (K + kXX6K - 1) / kXX6K;
   const int tq = (lane & 15) >> 2, tp = lane & 3, tg = lane >> 4;
-  const int kc = 8 * tg, kca = cw(lane & 15, kc);
+  const int kc = 8 * tg, kca = x6_swz(lane & 15, kc);
   for (int sl = 0; sl < nslab; ++sl) {
     if (sl + 1 < nslab) gload((sl + 1) * kXX6K);
     bf16x8 ah[2], am[2], al[2];
@@ -2683,24 +2616,12 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk_x6(GemmBatch batch) {
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      bf16x8 bp[3];
+      bf16x8 bp[3];   // the column block's h, m, l parts
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const s4t lo = lds_tr16(&sB[q][kc + tq][wn + j * 16 + 4 * tp]);
-        const s4t hi = lds_tr16(&sB[q][kc + tq + 4][wn + j * 16 + 4 * tp]);
-        const s8t v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        bp[q] = __builtin_bit_cast(bf16x8, v);
-      }
+      for (int q = 0; q < 3; ++q)
+        bp[q] = frag_tr16(&sB[q][kc + tq][wn + j * 16 + 4 * tp], &sB[q][kc + tq + 4][wn + j * 16 + 4 * tp]);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        f4 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bp[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bp[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bp[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bp[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bp[1], c, 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bp[0], c, 0, 0, 0);
-      }
+      for (int i = 0; i < 2; ++i) x6_mfma(acc[i][j], ah[i], am[i], al[i], bp[0], bp[1], bp[2]);
     }
     if (sl + 1 < nslab) {
       __syncthreads();   // every wave's fragment reads of this slab done
@@ -2710,39 +2631,38 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk_x6(GemmBatch batch) {
   }
   const bool writer = p == 0 && n0 == 0;
   if constexpr (AX) rows_finish<kXBM, NTH>(batch.rows, d, m0, writer, bid == 0, rows_x, s_q, s_coef, s_l);
-  // epilogue: coefficient, ReLU-backward mask, store (k_gemm's op order)
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int lr = wm + i * 16 + (lane >> 4) * 4 + r, row = m0 + lr;
-      const float cf = AX ? s_coef[d.ax_slot][lr] : 1.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int col = n0 + wn + j * 16 + (lane & 15);
-        float v = acc[i][j][r];
-        if (AX) v *= cf;
-        v = hm[i][j][r] > 0.f ? v : 0.f;
-        if (row < M && col < N) st_big(d.C + (size_t)row * d.ldc + col, v);
-      }
-    }
+  dh_epilogue<AX>(d, acc, hm, s_coef, m0, wm, n0 + wn, lane);
   if constexpr (AX) rows_loss<kXBM>(batch.rows, m0, writer, s_l);
 }
 
-// whether launch_gemm may run an fp32 level on k_axk_x6: k_axk16's level form in fp32 mode
-// (-1: no; else bit 0: the row-prologue form, bit 1: 64-wide tiles)
-static int axk_x6_ok(GemmBatch& b) {
-  if (b.bf16 || (b.ride.kind && b.ride.kind != 2) || b.ride.pk_blocks || b.has_adam) return -1;
+// the level form k_axk16 and k_axk_x6 take, dtype aside: every desc a dh GEMM of one kind
+// (1: the row-prologue form with the A transform; 0: the plain dh form) with K-contiguous
+// A, MN-contiguous 16-B aligned B and the mask epilogue, no ride but the gather.  -1: not
+// such a level.  (The A alignment, the bf16 operand flags and the tile counts: the callers.)
+static int dh_level_form(const GemmBatch& b) {
+  if (b.ride.kind && b.ride.kind != 2) return -1;   // (the dh kernels host the gather ride)
   const int ax = b.d[0].axk == 1 ? 1 : 0;
   if (ax != (b.rows.kind != 0 ? 1 : 0)) return -1;
   for (int i = 0; i < b.count; ++i) {
     const GemmDesc& d = b.d[i];
     if (d.axk != ax || !d.a_kc || d.b_kc || d.epi != EPI_MASK || d.bias || d.dotp || d.a_ksc ||
-        d.rs_col >= 0 || d.pa_out || d.a16 || d.b16 || d.c16 || d.x16)
+        d.rs_col >= 0)
       return -1;
-    if (((uintptr_t)d.A & 15) || (d.lda & 3) || ((uintptr_t)d.B & 15) || (d.ldb & 3) ||
-        (ax && ((uintptr_t)d.ax_w & 15)) || (d.N & 3))
+    if ((d.lda & 3) || ((uintptr_t)d.B & 15) || (d.ldb & 3) || (ax && ((uintptr_t)d.ax_w & 15)) || (d.N & 3))
       return -1;
+  }
+  return ax;
+}
+
+// whether launch_gemm may run an fp32 level on k_axk_x6: k_axk16's level form in fp32 mode
+// (-1: no; else bit 0: the row-prologue form, bit 1: 64-wide tiles)
+static int axk_x6_ok(GemmBatch& b) {
+  if (b.bf16 || b.ride.pk_blocks || b.has_adam) return -1;
+  const int ax = dh_level_form(b);
+  if (ax < 0) return -1;
+  for (int i = 0; i < b.count; ++i) {
+    const GemmDesc& d = b.d[i];
+    if (d.pa_out || d.a16 || d.b16 || d.c16 || d.x16 || ((uintptr_t)d.A & 15)) return -1;
   }
   // two workgroups per CU: 128-wide tiles where they give 512, else 64-wide ones (a one-net
   // level: the policy's dhp1; at 128 wide its 256 tiles measured slower than its k_gemm
@@ -2751,7 +2671,7 @@ static int axk_x6_ok(GemmBatch& b) {
   return assign_tiles<kXBM, 64>(b) >= 512 ? ax | 2 : -1;
 }
 
-static void launch_axk_x6(const GemmBatch& b, int form, hipStream_t s) {
+static void launch_axk_x6(GemmBatch& b, int form, hipStream_t s) {
   const dim3 grid(b.total_tiles + (b.ride.kind ? b.ride.nblocks : 0)), blk(64 * kAxWaves);
   switch (form) {
     case 0: hipLaunchKernelGGL((k_axk_x6<false>), grid, blk, 0, s, b); break;
@@ -2762,23 +2682,15 @@ static void launch_axk_x6(const GemmBatch& b, int form, hipStream_t s) {
   HIP_LAUNCH_CHECK();
 }
 
-// whether launch_gemm may run a level on k_axk16: bf16, every desc a row-prologue dh GEMM
-// (A transform, K-contiguous A, MN-contiguous 16-B aligned B, mask epilogue), no rides,
-// and at least one 64x128 tile per CU
+// whether launch_gemm may run a level on k_axk16: bf16, a dh level (dh_level_form) with A
+// rows aligned for the 4-element loads, and at least one 64x128 tile per CU
 // (-1: no; 1: the row-prologue form; 0: the plain dh form)
 static int axk16_ok(GemmBatch& b) {
-  if (!b.bf16 || (b.ride.kind && b.ride.kind != 2)) return -1;   // (hosts the gather ride)
-  const int ax = b.d[0].axk == 1 ? 1 : 0;
-  if (ax != (b.rows.kind != 0 ? 1 : 0)) return -1;
-  for (int i = 0; i < b.count; ++i) {
-    const GemmDesc& d = b.d[i];
-    if (d.axk != ax || !d.a_kc || d.b_kc || d.epi != EPI_MASK || d.bias || d.dotp || d.a_ksc ||
-        d.rs_col >= 0)
-      return -1;
-    if (((uintptr_t)d.A & (d.a16 ? 7 : 15)) || (d.lda & 3) || ((uintptr_t)d.B & 15) || (d.ldb & 3) ||
-        (ax && ((uintptr_t)d.ax_w & 15)) || (d.N & 3))
-      return -1;
-  }
+  if (!b.bf16) return -1;
+  const int ax = dh_level_form(b);
+  if (ax < 0) return -1;
+  for (int i = 0; i < b.count; ++i)
+    if ((uintptr_t)b.d[i].A & (b.d[i].a16 ? 7 : 15)) return -1;
   return assign_tiles<kXBM, kXBN>(b) >= 256 ? ax : -1;
 }
 
@@ -2907,59 +2819,77 @@ static int level_act16(const GemmBatch& b) {
   return any ? 1 : 0;
 }
 
-// bf16 deep-K weight-gradient levels: split count and workspace need, or 0 (k_gemm)
-static int dw_split_plan(GemmBatch& b, int64_t* stride) {
-  if (!b.ws) return 0;   // (bf16: k_dw_part16; fp32: k_dw_part_x6)
+// one split's partials in the workspace (floats): every desc's [M][dw_ncols]
+static int64_t dw_ws_stride(const GemmBatch& b) {
   int64_t el = 0;
+  for (int i = 0; i < b.count; ++i) el += (int64_t)b.d[i].M * dw_ncols(b.d[i]);
+  return el;
+}
+
+// deep-K weight-gradient levels: the split count (the workspace holds it), or -1 (k_gemm)
+static int dw_split_plan(GemmBatch& b) {
+  if (!b.ws) return -1;   // (bf16: k_dw_part16; fp32: k_dw_part_x6)
   int tiles = 0;
   for (int i = 0; i < b.count; ++i) {
     GemmDesc& d = b.d[i];
-    if (d.a_kc || d.b_kc || d.K < 2048 || d.axk) return 0;
-    if (d.epi != EPI_STORE && d.epi < EPI_ADAM) return 0;
+    if (d.a_kc || d.b_kc || d.K < 2048 || d.axk) return -1;
+    if (d.epi != EPI_STORE && d.epi < EPI_ADAM) return -1;
     // k_dw_fin's 4-column groups: the row-sum column is the bias column right after the
     // last output column, and output rows (and their Adam state) are 16-byte aligned with
     // room for a whole last group
     if ((d.rs_col >= 0 && d.rs_col != d.N) || (d.ldc & 3) || ((uintptr_t)d.C & 15) ||
         d.ldc < dw_ncols(d))
-      return 0;
+      return -1;
     if (d.epi >= EPI_ADAM && (((d.C - b.adam.P) & 3) || (b.adam.T && ((d.C - b.adam.P - b.adam.t_base) & 3))))
-      return 0;
+      return -1;
     d.tiles_m = (d.M + kDBM - 1) / kDBM;
     d.tiles_n = (d.N + kDBN - 1) / kDBN;
     d.tile_begin = tiles;
     tiles += d.tiles_m * d.tiles_n;
-    el += (int64_t)d.M * dw_ncols(d);
   }
   b.total_tiles = tiles;
-  if (el >= (1LL << 31)) return 0;
+  const int64_t el = dw_ws_stride(b);
+  if (el >= (1LL << 31)) return -1;
   // as many K splits as fit in one pass over the chip's workgroup slots (2 per CU at
   // 67 KB of LDS each): a partial second pass costs a whole slab loop (config 5: a
   // 528-workgroup L6 took 96 us, 440 workgroups 82 us)
   int ns = kDwTarget / tiles;
   ns = ns < 1 ? 1 : ns > kDwMaxSplit ? kDwMaxSplit : ns;
-  if ((int64_t)ns * el > b.ws_floats) return 0;
-  *stride = el;
-  return ns;
+  return (int64_t)ns * el > b.ws_floats ? -1 : ns;
 }
 
-// whether launch_gemm may run a level on k_fwd16 / k_fwd16p: bf16 plain forward GEMMs
-// (both operands K-contiguous, store / ReLU epilogue, optional bias and dot partials), no
-// prologue, no rides, and enough 128-row tiles to fill the chip.  (fp32 levels: the
-// 512-thread K-split k_gemm tiles measured faster — config 3: 1,351 vs 1,229 updates/s;
-// with bf16 MFMAs the levels are operand-traffic bound and the LDS sharing wins — config 5:
-// 1,381 -> 1,458.)
-static bool fwd_big_ok(GemmBatch& b) {
-  if (b.ride.kind || !b.bf16) return false;
+// the level form k_fwd16 / k_fwd16p and k_fwd_x6 take, dtype aside: plain forward GEMMs
+// (both operands K-contiguous, B 16-byte aligned, store / ReLU epilogue, optional bias and
+// dot partials over whole 32-column blocks), no prologue, no rides.  (The A alignment and
+// the bf16 operand flags: the callers.)
+static bool fwd_level_ok(const GemmBatch& b) {
+  if (b.ride.kind) return false;
   for (int i = 0; i < b.count; ++i) {
     const GemmDesc& d = b.d[i];
     if (!d.a_kc || !d.b_kc || d.axk || d.a_ksc || d.rs_col >= 0) return false;
-    if (((uintptr_t)d.A & (d.a16 ? 7 : 15)) || (d.lda & 3) || ((uintptr_t)d.B & 15) || (d.ldb & 3)) return false;
+    if ((d.lda & 3) || ((uintptr_t)d.B & 15) || (d.ldb & 3)) return false;
     if (d.epi != EPI_RELU && d.epi != EPI_STORE) return false;
     if (d.dotp && (d.N % 32)) return false;
   }
-  // 128-column tiles when they give two workgroups per CU, else 64-column ones
-  if (assign_tiles<kFBM, 128>(b) >= 512) return true;
-  return assign_tiles<kFBM, 64>(b) >= 512;
+  return true;
+}
+// its 128-row tiles: 128 columns wide when that gives two workgroups per CU, else 64; false
+// when neither does
+static bool fwd_level_tiles(GemmBatch& b) {
+  return assign_tiles<kFBM, 128>(b) >= 512 || assign_tiles<kFBM, 64>(b) >= 512;
+}
+
+// whether launch_gemm may run a level on k_fwd16 / k_fwd16p: bf16, a plain forward level
+// (fwd_level_ok) and enough 128-row tiles to fill the chip.  (fp32 levels: the
+// 512-thread K-split k_gemm tiles measured faster — config 3: 1,351 vs 1,229 updates/s;
+// with bf16 MFMAs the levels are operand-traffic bound and the LDS sharing wins — config 5:
+// 1,381 -> 1,458.)
+// (0: yes, the tile assignment of the chosen width left in b; -1: no)
+static int fwd_big_ok(GemmBatch& b) {
+  if (!b.bf16 || !fwd_level_ok(b)) return -1;
+  for (int i = 0; i < b.count; ++i)
+    if ((uintptr_t)b.d[i].A & (b.d[i].a16 ? 7 : 15)) return -1;
+  return fwd_level_tiles(b) ? 0 : -1;
 }
 
 // one k_gemm configuration, fp32 or bf16 MFMA operands
@@ -2978,7 +2908,8 @@ static bool all_bh(const GemmBatch& b) {
 }
 
 // the split-K weight-gradient level: k_dw_part16 (partials) + k_dw_fin (sum + epilogue)
-static void launch_dw_split(GemmBatch& b, int ns, int64_t stride, hipStream_t s) {
+static void launch_dw_split(GemmBatch& b, int ns, hipStream_t s) {
+  const int64_t stride = dw_ws_stride(b);
   if (b.ride.pk_blocks) throw Error{SACMI_ESTATE, "Polyak ride on a level outside k_gemm"};
   const int ride = b.ride.kind ? b.ride.nblocks : 0;
   if (b.ride.kind == 1 && mt_sample_lds_words(b.ride.tbl_log2, b.ride.mt.setsize) * 4 > (size_t)kDw16LdsBytes)
@@ -3019,7 +2950,7 @@ static void launch_dw_split(GemmBatch& b, int ns, int64_t stride, hipStream_t s)
 }
 
 // the batch-4096-class dh level: k_axk16 (axk16_ok form `ax`)
-static void launch_axk16(const GemmBatch& b, int ax, hipStream_t s) {
+static void launch_axk16(GemmBatch& b, int ax, hipStream_t s) {
   if (b.ride.pk_blocks) throw Error{SACMI_ESTATE, "Polyak ride on a level outside k_gemm"};
   for (int i = 0; i < b.count; ++i)   // k_axk16 computes no dL/da partials
     if (b.d[i].pa_out) throw Error{SACMI_ESTATE, "dL/da partials requested on a k_axk16 level"};
@@ -3049,7 +2980,7 @@ static void launch_axk16(const GemmBatch& b, int ax, hipStream_t s) {
 // the batch-4096-class bf16 forward level: k_fwd16p (multi-slab LDS ring) where its plan
 // applies, else k_fwd16.  SACMI_NO_FWD16P (read once): k_fwd16 only — the parity test that
 // holds the two kernels to the same bits (tests/test_gpu_fwd16p.py)
-static void launch_fwd16(GemmBatch& b, hipStream_t s) {
+static void launch_fwd16(GemmBatch& b, int, hipStream_t s) {
   if (b.ride.pk_blocks) throw Error{SACMI_ESTATE, "Polyak ride on a level outside k_gemm"};
   const bool n128 = b.d[0].tiles_n * kFBN128 >= b.d[0].N && b.d[0].tiles_n == (b.d[0].N + 127) / 128;
   const bool bh = all_bh(b);
@@ -3085,25 +3016,19 @@ static void launch_fwd16(GemmBatch& b, hipStream_t s) {
   HIP_LAUNCH_CHECK();
 }
 
-// whether launch_gemm may run an fp32 level on k_fwd_x6: plain forward GEMMs (both operands
-// K-contiguous and 16-byte aligned, store / ReLU epilogue, optional bias and dot partials),
-// no prologue, no rides, and two 128-row tiles per CU (128 columns wide where that gives
-// them, else 64).  The tile assignment of the chosen width is left in b.
-static bool fwd_x6_ok(GemmBatch& b) {
-  if (b.ride.kind || b.ride.pk_blocks || b.bf16 || b.has_adam) return false;
+// whether launch_gemm may run an fp32 level on k_fwd_x6: a plain forward level
+// (fwd_level_ok) with 16-byte aligned A rows, and two 128-row tiles per CU.
+// (0: yes, the tile assignment of the chosen width left in b; -1: no)
+static int fwd_x6_ok(GemmBatch& b) {
+  if (b.bf16 || b.ride.pk_blocks || b.has_adam || !fwd_level_ok(b)) return -1;
   for (int i = 0; i < b.count; ++i) {
     const GemmDesc& d = b.d[i];
-    if (!d.a_kc || !d.b_kc || d.axk || d.a_ksc || d.rs_col >= 0 || d.pa_out) return false;
-    if (d.a16 || d.b16 || d.c16 || d.x16) return false;
-    if (((uintptr_t)d.A & 15) || (d.lda & 3) || ((uintptr_t)d.B & 15) || (d.ldb & 3)) return false;
-    if (d.epi != EPI_RELU && d.epi != EPI_STORE) return false;
-    if (d.dotp && (d.N % 32)) return false;
+    if (d.pa_out || d.a16 || d.b16 || d.c16 || d.x16 || ((uintptr_t)d.A & 15)) return -1;
   }
-  if (assign_tiles<kFBM, 128>(b) >= 512) return true;
-  return assign_tiles<kFBM, 64>(b) >= 512;
+  return fwd_level_tiles(b) ? 0 : -1;
 }
 
-static void launch_fwd_x6(const GemmBatch& b, hipStream_t s) {
+static void launch_fwd_x6(GemmBatch& b, int, hipStream_t s) {
   const bool n128 = b.d[0].tiles_n == (b.d[0].N + 127) / 128;
   const dim3 g(b.total_tiles), blk(64 * kX6Waves);
   if (n128) hipLaunchKernelGGL(k_fwd_x6<128>, g, blk, 0, s, b);
@@ -3113,38 +3038,19 @@ static void launch_fwd_x6(const GemmBatch& b, hipStream_t s) {
 
 void launch_gemm(const GemmBatch& b0, hipStream_t s) {
   if (b0.count == 0) return;
-  GemmBatch b = b0;
-  {
-    int64_t stride = 0;
-    const int ns = dw_split_plan(b, &stride);
-    if (ns > 0) {
-      launch_dw_split(b, ns, stride, s);
-      return;
-    }
-  }
-  b = b0;
-  {
-    const int ax = axk16_ok(b);
-    if (ax >= 0) {
-      launch_axk16(b, ax, s);
-      return;
-    }
-  }
-  b = b0;
-  if (fwd_big_ok(b)) {
-    launch_fwd16(b, s);
-    return;
-  }
-  b = b0;
-  if (fwd_x6_ok(b)) {
-    launch_fwd_x6(b, s);
-    return;
-  }
-  b = b0;
-  {
-    const int ax = axk_x6_ok(b);
-    if (ax >= 0) {
-      launch_axk_x6(b, ax, s);
+  // the batch-4096-class kernels, in this order: the first whose probe takes the level
+  // (form >= 0) runs it.  A probe writes its tile assignment into b: each starts from b0.
+  static constexpr struct {
+    int (*probe)(GemmBatch&);
+    void (*launch)(GemmBatch&, int form, hipStream_t);
+  } kBig[] = {{dw_split_plan, launch_dw_split}, {axk16_ok, launch_axk16}, {fwd_big_ok, launch_fwd16},
+              {fwd_x6_ok, launch_fwd_x6}, {axk_x6_ok, launch_axk_x6}};
+  GemmBatch b;
+  for (const auto& k : kBig) {
+    b = b0;
+    const int form = k.probe(b);
+    if (form >= 0) {
+      k.launch(b, form, s);
       return;
     }
   }

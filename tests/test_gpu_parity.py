@@ -740,7 +740,8 @@ def _check_bf16_update(cfg, lb, gb, emu, exact, l_emu):
 
 
 @pytest.mark.parametrize("S,A,n_hidden,B", [(376, 17, 2, 256), (376, 17, 3, 256), (376, 17, 2, 4096),
-                                           (376, 17, 3, 4096), (661, 23, 2, 4096)])
+                                           (376, 17, 3, 4096), (661, 23, 2, 4096),
+                                           (376, 17, 2, 3000), (376, 17, 2, 4100)])
 def test_bf16_compute_vs_emulation(S, A, n_hidden, B):
     """compute_dtype bf16 (BASELINE configs[4]; (661, 23, 512, B=4096): configs[4]'s own
     NAO shapes): bf16 MFMA operands, fp32 accumulation, fp32 master weights / Adam / losses.

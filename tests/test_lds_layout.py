@@ -1,6 +1,6 @@
 """Host-side check of the x6 kernels' LDS layout (no GPU): the XOR chunk swizzle of
-k_fwd_x6's planes and k_axk_x6's A planes, read from kernels.hip, is a permutation of each
-64-byte row's 16-byte chunks, and it is bank-conflict-free for the two access patterns the
+k_fwd_x6's planes and k_axk_x6's A planes (x6_swz, read from kernels.hip) is a permutation
+of each 64-byte row's 16-byte chunks, and it is bank-conflict-free for the two access patterns the
 kernels issue — the ds_read_b128 fragment reads (row = lane & 15 of a 16-row block, chunk =
 lane >> 4) in the lane groups of MI355X_MICROARCH.md §LDS, and the staging ds_write_b64
 stores (8 threads a row, 4 bf16 each) in 16-lane contiguous groups.  The layout is the one
@@ -22,9 +22,13 @@ B128_GROUPS = [
 
 def swizzle_fns():
     src = KERNELS.read_text()
-    exprs = re.findall(r"auto cw = \[\]\(int r, int k\) \{ return (.+?); \};", src)
-    assert len(exprs) == 2, "k_fwd_x6 and k_axk_x6 each define the chunk swizzle"
-    assert exprs[0] == exprs[1], "one layout for both kernels"
+    exprs = re.findall(r"int x6_swz\(int r, int k\) \{ return (.+?); \}", src)
+    assert len(exprs) == 1, "one definition of the chunk swizzle"
+    assert "auto cw =" not in src, "no per-kernel copy of the swizzle"
+    for kernel in ("k_fwd_x6", "k_axk_x6"):      # both kernels address their planes through it
+        body = src[src.index(f"void {kernel}(GemmBatch batch)"):]
+        body = body[:body.index("\n}\n")]
+        assert "x6_swz(" in body, kernel
     expr = exprs[0]
     assert re.fullmatch(r"[\s\d()<>&^|rk+\-*]+", expr), expr     # plain integer arithmetic
     return expr, eval(f"lambda r, k: {expr}")
