@@ -1591,10 +1591,15 @@ __global__ __launch_bounds__(64 * fwd16_waves<kFBN>(), 2) void k_fwd16(GemmBatch
 // ---------------------------------------------------------------------------
 // fp32 forward levels of the batch-4096 class on bf16 MFMA: the exact three-way split
 // ("x6").  gfx950 has no xf32 MFMA and its fp32 MFMA issues at 1/16 of the bf16 rate.  Each
-// fp32 operand x is cut EXACTLY into three bf16 parts x = h + m + l by truncation (h: the
-// top 8 significant bits; m: the next 8 of the remainder; l: the rest, at most 8 bits — both
+// fp32 operand x is cut into three bf16 parts x = h + m + l by truncation (h: the top 8
+// significant bits; m: the next 8 of the remainder; l: the rest, at most 8 bits — both
 // subtractions exact in fp32), once per workgroup as the slab is staged, into three bf16 LDS
-// planes per operand.  a.b is then 9 cross products of exact parts; the 6 kept (hh, hm, mh,
+// planes per operand.  The cut is exact for x == 0 and |x| >= 2^-110; below that the
+// remainders are fp32 subnormals whose bits under 2^-133 no bf16 holds, and the truncation
+// drops them (up to 16 bits of x, toward zero; the workload produces no such operands).
+// oracle/x6_model.py repeats the split and the kept products operation for operation, and
+// tests/test_x6_model.py pins the domain, the bound below and this source to that model.
+// a.b is then 9 cross products of exact parts; the 6 kept (hh, hm, mh,
 // mm, hl, lh) are exact products summed in the fp32 accumulator.  With truncation
 // |m| < 2^-7 |x| and |l| < 2^-15 |x|, so the 3 dropped (ml, lm, ll) are bounded by about
 // 2^-21 |a b| per product — some 8 fp32 ulps, not below the unit roundoff — and, every
@@ -1643,17 +1648,29 @@ __device__ __forceinline__ void x6_store3(__bf16* ph, __bf16* pm, __bf16* pl, fl
   *reinterpret_cast<u2v*>(pl) = l;
 }
 
-// the six kept products of one 16x16x32 block, small terms first into the accumulator (the
-// order is part of the result's bits: one chain for every x6 kernel)
+// the six kept products of one 16x16x32 block, small terms first (the order is part of the
+// result's bits).  SLAB false: chained through the running accumulator.  SLAB true (the
+// forward kernel, whose outputs tests/test_gpu_x6.py holds to the model elementwise): summed
+// on their own from zero and added to the accumulator once.  The MFMA rounds as it
+// accumulates; chained through the accumulator every one of those roundings is at the
+// accumulator's magnitude (|gpu - model| 1.0e-6 to 1.5e-6 of sum|a||b| on same-sign K = 512
+// dots, twice the fp32 reference's), while a slab's own sum is rounded at the slab's
+// magnitude and the accumulator takes one rounding a slab (3.3e-7).  The dh
+// and weight-gradient kernels keep the chained form: their 125-127 registers leave no room
+// for the temporary (scratch spills, config 3 -5 % with all three kernels on the slab form).
+template <bool SLAB = false>
 __device__ __forceinline__ void x6_mfma(f4& acc, bf16x8 ah, bf16x8 am, bf16x8 al, bf16x8 bh,
                                         bf16x8 bm, bf16x8 bl) {
   f4 c = acc;
+  if constexpr (SLAB) c = f4{0.f, 0.f, 0.f, 0.f};
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, c, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+  if constexpr (SLAB) acc += c;
+  else acc = c;
 }
 
 // column of element k in row r of a [row][k] plane (k_fwd_x6's planes, k_axk_x6's A planes):
@@ -1663,7 +1680,7 @@ __device__ __forceinline__ void x6_mfma(f4& acc, bf16x8 ah, bf16x8 am, bf16x8 al
 __device__ __forceinline__ int x6_swz(int r, int k) { return (((k >> 3) ^ ((r >> 2) & 2)) << 3) | (k & 7); }
 
 template <int BN>
-__global__ __launch_bounds__(64 * kX6Waves, 2) void k_fwd_x6(GemmBatch batch) {
+__global__ __launch_bounds__(64 * kX6Waves, 4) void k_fwd_x6(GemmBatch batch) {
   const TlMark tl_mark(batch.tl, TL_FWD_X6);
   constexpr int NWV = kX6Waves, WC = 2, WR = NWV / WC;
   constexpr int MW = kFBM / WR, MI = MW / 16, NW = BN / WC, NT = NW / 16;
@@ -1741,7 +1758,7 @@ __global__ __launch_bounds__(64 * kX6Waves, 2) void k_fwd_x6(GemmBatch batch) {
       const bf16x8 bm = *reinterpret_cast<const bf16x8*>(&sB[1][r][kc]);
       const bf16x8 bl = *reinterpret_cast<const bf16x8*>(&sB[2][r][kc]);
 #pragma unroll
-      for (int i = 0; i < MI; ++i) x6_mfma(acc[i][j], ah[i], am[i], al[i], bh, bm, bl);
+      for (int i = 0; i < MI; ++i) x6_mfma<true>(acc[i][j], ah[i], am[i], al[i], bh, bm, bl);
     }
     if (sl + 1 < nslab) {
       __syncthreads();   // every wave's fragment reads of this slab done

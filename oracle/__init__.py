@@ -16,6 +16,9 @@ sac_step   functional torch-CPU restatement of ``SAC.update_parameters``
            fp64, with injected minibatch / eps so one step is fully determined.
 per        numpy restatement of ``PrioritizedReplayBuffer`` sample / push /
            update_priorities (reference ``replay_buffer.py:25-90``).
+x6_model   bit-faithful numpy model of the batch-4096 fp32 GEMM kernels' three-way bf16
+           operand split and six-product dot (kernels.hip x6_split4 / x6_mfma), with
+           the adversarial-mantissa input classes of the x6 tests.
 replay_ref deque-of-tuples uniform buffer with the reference's data path
            (``replay_buffer.py:5-22``), used only to time the CPU baseline.
 

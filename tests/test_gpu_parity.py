@@ -1369,19 +1369,12 @@ def gpu_relu_masks(ctx, cfg, B):
     return masks
 
 
-@pytest.mark.parametrize("n_hidden,B", [(2, 4096), (3, 4096), (2, 3000)])
-def test_step_humanoid_b4096_under_gpu_masks(n_hidden, B):
-    """Batch 4096 (BASELINE configs[2] shapes) at the 1e-5 gradient bar — and batch 3000, whose
-    row counts are no multiple of the x6 kernels' 128-row tiles (k_fwd_x6's clamped rows, the
-    split-K ranges of k_dw_part_x6; the dh levels fall back to k_gemm): the fp64 truth is
-    recomputed under the GPU's OWN ReLU masks (read back from the activations the update left
-    in HBM).  Where test_step_humanoid_b4096_vs_oracle needs its ReLU-flip allowances
-    (q1.fc1.weight 2.9e-4 against plain fp64), the flips are the whole story if every gradient
-    tensor sits within 1e-5 of this masked truth; the number of flipped decisions per pass is
-    printed with the per-tensor table."""
-    cfg = SacConfig(376, 17, 512, n_hidden=n_hidden)
-    params = init_params(cfg, 101, bias_scale=0.02)
-    rows = synthetic_rows(cfg, 6000, 102, state_scale=0.1)
+def check_update_under_gpu_masks(cfg, params, rows, B, name, after_readback=None):
+    """One update of batch B on `rows` (host-given minibatch and noise) against fp64 evaluated
+    under the GPU's own ReLU masks: every flipped decision within FLIP_Z_TOL of zero, losses
+    within LOSS_TOL, every gradient tensor within MASKED_GRAD_TOL.  after_readback(ctx) runs
+    once the update's gradients and activations are read (a hook for checks that run further
+    updates on the context, such as the launch timeline)."""
     ctx = make_ctx(cfg, max_batch=B, capacity=len(rows[2]))
     load_params(ctx, params)
     ctx.push(*rows)
@@ -1392,6 +1385,8 @@ def test_step_humanoid_b4096_under_gpu_masks(n_hidden, B):
     lg = ctx.step(B, idx=idx, eps1=e1, eps2=e2)
     gg = ctx_grads(ctx, cfg)
     masks = gpu_relu_masks(ctx, cfg, B)
+    if after_readback is not None:
+        after_readback(ctx)
     batch = [x[idx] for x in rows]
     om = OracleSAC(cfg, params, torch.float64)
     lm = om.step(*batch, e1, e2, masks=masks)
@@ -1405,8 +1400,26 @@ def test_step_humanoid_b4096_under_gpu_masks(n_hidden, B):
     for i, k in enumerate(("q1_loss", "q2_loss", "policy_loss")):
         assert abs(lg[i] - lm[k]) <= LOSS_TOL * max(abs(lm[k]), 1e-3), (k, lg[i], lm[k])
     table = {k: (rel(gg[k], v), rel(gg[k], g64[k])) for k, v in gm.items()}
-    report_grad_errors(f"humanoid B{B} n_hidden {n_hidden} under the GPU's ReLU masks", MASKED_GRAD_TOL, table,
+    report_grad_errors(f"{name} under the GPU's ReLU masks", MASKED_GRAD_TOL, table,
                        second="gpu_vs_plain_fp64", strict=True)
     bad = {k: e for k, (e, _) in table.items() if e > MASKED_GRAD_TOL}
     assert not bad, bad
     ctx.close()
+
+
+@pytest.mark.parametrize("n_hidden,B", [(2, 4096), (3, 4096), (2, 3000)])
+def test_step_humanoid_b4096_under_gpu_masks(n_hidden, B):
+    """Batch 4096 (BASELINE configs[2] shapes) at the 1e-5 gradient bar — and batch 3000, whose
+    row counts are no multiple of the x6 kernels' 128-row tiles (k_fwd_x6's clamped rows on L1 /
+    L2, k_axk_x6 on the critic dh levels L5 / L9, the split-K ranges of k_dw_part_x6; by the
+    launch timeline the twin-critic forward levels L3 / L4 / L7 / L8 — 2 x 24 x 8 = 384 tiles,
+    under k_fwd_x6's 512 — and the policy dh level L12 fall back to k_gemm): the fp64 truth is
+    recomputed under the GPU's OWN ReLU masks (read back from the activations the update left
+    in HBM).  Where test_step_humanoid_b4096_vs_oracle needs its ReLU-flip allowances
+    (q1.fc1.weight 2.9e-4 against plain fp64), the flips are the whole story if every gradient
+    tensor sits within 1e-5 of this masked truth; the number of flipped decisions per pass is
+    printed with the per-tensor table."""
+    cfg = SacConfig(376, 17, 512, n_hidden=n_hidden)
+    params = init_params(cfg, 101, bias_scale=0.02)
+    rows = synthetic_rows(cfg, 6000, 102, state_scale=0.1)
+    check_update_under_gpu_masks(cfg, params, rows, B, f"humanoid B{B} n_hidden {n_hidden}")
