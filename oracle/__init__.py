@@ -19,6 +19,10 @@ per        numpy restatement of ``PrioritizedReplayBuffer`` sample / push /
 x6_model   bit-faithful numpy model of the batch-4096 fp32 GEMM kernels' three-way bf16
            operand split and six-product dot (kernels.hip x6_split4 / x6_mfma), with
            the adversarial-mantissa input classes of the x6 tests.
+heads_model analytic numpy model of the policy sample head (clamp, tanh squash, log-prob)
+           and its backward as the HIP head kernels state them, in float32 or float64:
+           the yardstick of the head-edge tests (tests/test_heads_model.py ties it to
+           torch float64 autograd of sac_step._policy_sample).
 replay_ref deque-of-tuples uniform buffer with the reference's data path
            (``replay_buffer.py:5-22``), used only to time the CPU baseline.
 

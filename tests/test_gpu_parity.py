@@ -50,6 +50,8 @@ def rel(a, b):
 
 def make_ctx(cfg: SacConfig, max_batch, capacity, **kw):
     from sacmi import Config, Context
+    kw.setdefault("action_low", cfg.action_low)
+    kw.setdefault("action_high", cfg.action_high)
     c = Config(cfg.state_dim, cfg.action_dim, cfg.hidden_dim, max_batch=max_batch,
                gamma=cfg.gamma, tau=cfg.tau, lr=cfg.lr, alpha=cfg.alpha,
                automatic_entropy_tuning=cfg.automatic_entropy_tuning, capacity=capacity,
