@@ -377,10 +377,16 @@ __device__ __forceinline__ void place_tile(const GemmDesc& d, int t, int& tr, in
 
 // layout dispatch (wave-uniform, once per workgroup)
 // AXK: whether this kernel instantiation carries the A-transform path (launch_gemm picks
-// the variant from the level's descs): 1 -> axk 1 descs, 0 -> none.
+// the variant from the level's descs): 1 -> axk 1 descs among others, 0 -> none, 2 -> every
+// desc is a plain axk 1 dh desc (axk_level_static): the one core that runs, nothing else.
 template <int TM, int TN, int KSPLIT, int G, int MG, int AXK, bool BF16, class Pre>
 __device__ __forceinline__ void gemm_core(const GemmDesc& d, int m0, int n0, float* red,
                                           float* rsum, bool rowsum, Pre&& pre) {
+  if constexpr (AXK == 2) {
+    gemm_core_l<TM, TN, KSPLIT, G, true, false, false, MG, 1, BF16>(d, m0, n0, red, rsum, pre,
+                                                                  n0 == 0 && d.ax_out != nullptr);
+    return;
+  }
   if constexpr (AXK == 1) {
     if (d.axk == 1) {   // fc3 backward folded into dh1 / dha1 (A = h2, B = W2)
       gemm_core_l<TM, TN, KSPLIT, G, true, false, false, MG, 1, BF16>(d, m0, n0, red, rsum, pre,
@@ -755,6 +761,134 @@ __device__ __forceinline__ void rows_loss(const RowsFuse& rf, int m0, bool write
   }
 }
 
+// The row prologue of a level whose every desc is axk 1 (k_gemm AXK 2), same values as
+// rows_load / rows_finish in far fewer registers and one barrier:
+//  * the TMW * nslot * 16 dot partials are spread over the whole workgroup, two per thread
+//    (eight lanes per (row, slot): lane j holds partials j and j + 8), and summed in
+//    column order inside the wave that loaded them, by lane shuffles — no thread carries
+//    16 of them across the MFMA phase;
+//  * every thread loads the inputs of ITS epilogue row (TN threads per row) and forms the
+//    row's coefficients itself from the head sums in LDS: one barrier between the K loop
+//    and the epilogue (the one the K-split reduction needs anyway);
+//  * plain global loads at clamped indices (the base pointers stay in SGPR pairs: no
+//    buffer descriptors).
+struct Rows2Regs {
+  float pv[2];                // lane j of an eight-lane (row, slot) group: partials j, j + 8
+  float r, d, lp, alpha;      // the thread's epilogue row
+  float lpa;                  // actor block 0, the wave past the (row, slot) threads: logp_part[lane]
+};
+
+template <int TMW, int TN>
+__device__ __forceinline__ void rows2_load(const RowsFuse& rf, int m0, Rows2Regs& x) {
+  const int t = threadIdx.x;
+  const bool critic = rf.kind == 1;
+  const int nslot = critic ? 4 : 2;
+  {
+    const int pr = t >> 3, j = t & 7;
+    const int row = critic ? pr >> 2 : pr >> 1, sl = critic ? pr & 3 : pr & 1;
+    const bool ok = pr < TMW * nslot && m0 + row < rf.B;
+    const uint32_t base = (uint32_t)(((size_t)sl * rf.B + m0 + row) * rf.nparts);
+    x.pv[0] = rf.part[ok && j < rf.nparts ? base + j : 0u];
+    x.pv[1] = rf.part[ok && j + 8 < rf.nparts ? base + j + 8 : 0u];
+  }
+  const int b = m0 + t / TN;
+  const uint32_t ob = (uint32_t)(b < rf.B ? b : 0);
+  // (a lane-varying zero: a uniform address would become a scalar load the compiler is free
+  // to hoist in front of the operand loads)
+  uint32_t z = 0;
+  asm volatile("" : "+v"(z));
+  x.alpha = (&rf.sc->alpha)[z];
+  x.lp = rf.logp[ob];
+  x.r = (critic ? rf.r : rf.logp)[ob];
+  x.d = (critic ? rf.d : rf.logp)[ob];
+  const int lane = t - TMW * nslot;
+  x.lpa = (rf.logp_part ? rf.logp_part : rf.logp)[lane >= 0 && lane < rf.n_lp ? (uint32_t)(2 * lane + 1) : 0u];
+}
+
+// after the MFMAs, before the workgroup's barrier: the head sums to s_q, and block 0 of
+// an actor level its scalar work (as in rows_finish)
+template <int TMW>
+__device__ __forceinline__ void rows2_sum(const RowsFuse& rf, int m0, bool first_block, Rows2Regs& x,
+                                          float (*s_q)[4]) {
+  const int t = threadIdx.x;
+  const bool critic = rf.kind == 1;
+  const int nslot = critic ? 4 : 2;
+  // pin every prologue value to this point (see rows_finish)
+  asm volatile("" : "+v"(x.pv[0]), "+v"(x.pv[1]), "+v"(x.r), "+v"(x.d), "+v"(x.lp), "+v"(x.lpa), "+v"(x.alpha));
+  {
+    const int pr = t >> 3;
+    const int row = critic ? pr >> 2 : pr >> 1, sl = critic ? pr & 3 : pr & 1;
+    const bool ok = pr < TMW * nslot && m0 + row < rf.B;
+    const int l0 = t & 56;      // the group's first lane
+    float s[kRowsPv];
+#pragma unroll
+    for (int i = 0; i < kRowsPv; ++i) s[i] = __shfl(x.pv[i >> 3], l0 + (i & 7), 64);
+    // the row's partials summed in column order (block 0's carries the fc3 bias)
+    float acc = s[0];
+#pragma unroll
+    for (int i = 1; i < kRowsPv; ++i)
+      if (i < rf.nparts) acc += s[i];
+    if (ok) {
+      for (int i = kRowsPv; i < rf.nparts; ++i)     // H > 512 only
+        acc += rf.part[((size_t)sl * rf.B + m0 + row) * rf.nparts + i];
+    }
+    if ((t & 7) == 0 && pr < TMW * nslot) s_q[row][sl] = ok ? acc : 0.f;
+  }
+  if (first_block && rf.kind == 2) {
+    const int w0 = TMW * nslot;            // first wave past the partial-sum threads
+    if (t >= w0 && t < w0 + 64) {
+      // dL/dlog_alpha and the step counters: rows_finish's block, unchanged
+      const int lane = t - w0;
+      float acc = 0.f;
+      if (rf.alpha_grad) {
+        if (lane < rf.n_lp) acc += x.lpa;
+        for (int w = lane + 64; w < rf.n_lp; w += 64) acc += rf.logp_part[2 * w + 1];
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+      if (lane == 0) {
+        if (rf.alpha_grad) *rf.alpha_grad = -(acc + (float)rf.B * rf.target_entropy) / (float)rf.B;
+        const int err = rf.sc->err;
+        const bool any = (err & kErrSkipAll) == 0;
+        const bool all = any && (err & kErrActLike) == 0;
+        for (int i = 0; i < 4; ++i) {
+          const bool adv = all || (any && (i == 1 || i == 2));
+          rf.sc->step[i] += adv ? 1.0 : 0.0;
+          rf.sc->beta_pow[i][0] *= adv ? 0.9 : 1.0;   // torch Adam default betas (sac_imp.py:39-49)
+          rf.sc->beta_pow[i][1] *= adv ? 0.999 : 1.0;
+        }
+        rf.sc->noise_counter += all ? 1 : 0;
+        if (any && !all) atomicOr(&rf.sc->err, (int)ERR_ABORT);
+      }
+    }
+  }
+}
+
+// after the barrier: the coefficients (c0, c1) and loss terms of batch row b from its head
+// sums q[0..3] — rows_finish's arithmetic, expression for expression
+__device__ __forceinline__ void rows2_coef(const RowsFuse& rf, int b, const float* q, const Rows2Regs& x,
+                                           float& c0, float& c1, float& l0, float& l1) {
+  c0 = 0.f; c1 = 0.f; l0 = 0.f; l1 = 0.f;
+  if (b < rf.B) {
+    if (rf.kind == 1) {
+      const float vt = fminf(q[2], q[3]) - x.alpha * x.lp;
+      const float qhat = x.r + ((1.f - x.d) * rf.gamma) * vt;
+      const float e1 = q[0] - qhat, e2 = q[1] - qhat;
+      c0 = 2.f * e1 / (float)rf.B;
+      c1 = 2.f * e2 / (float)rf.B;
+      l0 = e1 * e1;
+      l1 = e2 * e2;
+    } else {
+      const float q1 = q[0], q2 = q[1];
+      l0 = x.alpha * x.lp - fminf(q1, q2);
+      const float g = -1.f / (float)rf.B;
+      const float w1 = q1 < q2 ? 1.f : (q1 == q2 ? 0.5f : 0.f);
+      c0 = g * w1;
+      c1 = g * (1.f - w1);
+    }
+  }
+}
+
 // data-parallel phase 0: the update's error flags for the critic gradient collective
 // (kDpFlagN; GemmBatch::err_flags).  Every error source of the update ran before this level.
 __device__ __forceinline__ void store_err_flags(const GemmBatch& b) {
@@ -885,7 +1019,7 @@ constexpr int gemm_threads() { return 64 * KSPLIT * MG; }
 template <int TM, int TN, int KSPLIT, int MG, int AXK>
 struct KgSmem {
   static constexpr int TMW = TM * MG;
-  static constexpr bool PA = AXK == 1 && MG == 1;
+  static constexpr bool PA = AXK >= 1 && MG == 1;
   float red[MG * KSPLIT * TM * (TN + 1)];
   float rsum[MG * KSPLIT * TM];
   AdamScalars s_k;
@@ -915,7 +1049,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   for (int q = 0; q < kMaxGemms; ++q) asm volatile("" :: "s"(tbeg[q]));
   // ... with the level-wide epilogue scalars that do not depend on the desc (the row
   // prologue's / fused Adam's pointers): otherwise their loads sit behind the desc's
-  if constexpr (AXK == 1) {
+  if constexpr (AXK >= 1) {
     const RowsFuse& r = batch.rows;
     asm volatile("" :: "s"(r.part), "s"(r.logp), "s"(r.r), "s"(r.d), "s"(r.kind), "s"(r.nparts),
                  "s"(r.B), "s"(r.sc), "s"(r.logp_part), "s"(r.n_lp));
@@ -937,7 +1071,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   auto& s_dotw = sm.s_dotw;
   // dL/da partials (axk-1 levels of one 32-row wave group): the tile's outputs [TMW][TN+1]
   // and its fc1 action weights [TN][32]
-  constexpr bool PA = AXK == 1 && MG == 1;
+  constexpr bool PA = AXK >= 1 && MG == 1;
   float* const s_pa = sm.s_pa;
   if (bid >= n_tiles) {   // ride-along workgroups (next update's replay work, Polyak)
     if constexpr (gemm_threads<KSPLIT, MG>() == 1024) {   // the host attaches rides to 1024-thread configs
@@ -978,7 +1112,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
     asm volatile("" :: SACMI_DESC_PIN_K, SACMI_DESC_PIN_E, "s"(a.P), "s"(a.M), "s"(a.V), "s"(a.T),
                  "s"(a.G), "s"(a.t_base), "s"(a.lr), "s"(a.beta1), "s"(a.beta2), "s"(a.eps),
                  "s"(a.tau), "s"(a.step_offset), "s"(a.sc), "s"(d.adam_step));
-  } else if constexpr (AXK == 1) {
+  } else if constexpr (AXK >= 1) {
     const RowsFuse& r = batch.rows;
     asm volatile("" :: SACMI_DESC_PIN_K, SACMI_DESC_PIN_E, "s"(d.pa_w), "s"(d.pa_out), "s"(d.pa_ld),
                  "s"(d.pa_A), "s"(d.pa_base), "s"(r.part), "s"(r.logp), "s"(r.r), "s"(r.d),
@@ -1004,7 +1138,11 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
                        1.f - a.beta2);
     }
   }
-  const bool rowsum = d.rs_col >= 0 && n0 == 0;
+  // AXK 2: every desc is a plain dh desc (axk 1, mask epilogue, no bias, no bias-gradient
+  // column, no dot partials: axk_level_static) — what the other forms select at run time,
+  // and build a zero-length descriptor for, is not compiled at all
+  constexpr bool AXA = AXK == 2;
+  const bool rowsum = !AXA && d.rs_col >= 0 && n0 == 0;
   const AdamFuse& af = batch.adam;
   // Adam bias corrections and the error bits: thread 0 reads them in pre(), behind its
   // wave's operand loads (at the kernel's start they put a device-memory round trip in
@@ -1035,7 +1173,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   // byte span of this desc's output (tile rows, plus the rowsum column; the fused-Adam
   // 4-column groups reach the row's padding up to a multiple of 4: ldc is one)
   const int ncov = ADAM ? (d.N + 3) & ~3 : d.N;
-  const uint32_t span = (uint32_t)(((size_t)(d.M - 1) * d.ldc + (d.rs_col >= ncov ? d.rs_col + 1 : ncov)) * 4);
+  const uint32_t span = (uint32_t)(((size_t)(d.M - 1) * d.ldc + (!AXA && d.rs_col >= ncov ? d.rs_col + 1 : ncov)) * 4);
   const size_t abase = ADAM ? (size_t)(d.C - af.P) : 0;
   const rsrc_t rC = make_rsrc(d.C, span);
   // (unused descriptors get a zero-length range: any access through them is dropped)
@@ -1043,8 +1181,8 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   const rsrc_t rV = make_rsrc(ADAM ? af.V + abase : d.C, ADAM ? span : 0);
   const rsrc_t rT = make_rsrc(ADAM && pol ? af.T + abase - af.t_base : d.C, ADAM && pol ? span : 0);
   const rsrc_t rG = make_rsrc(ADAM && af.G ? af.G + abase : d.C, ADAM && af.G ? span : 0);
-  const rsrc_t rX = d.bias ? make_rsrc(d.bias, (uint32_t)(((size_t)(d.N - 1) * d.bias_ld + 1) * 4))
-                  : d.epi == EPI_MASK ? make_rsrc(d.aux, (uint32_t)(((size_t)(d.M - 1) * d.ldaux + d.N) * 4))
+  const rsrc_t rX = !AXA && d.bias ? make_rsrc(d.bias, (uint32_t)(((size_t)(d.N - 1) * d.bias_ld + 1) * 4))
+                  : AXA || d.epi == EPI_MASK ? make_rsrc(d.aux, (uint32_t)(((size_t)(d.M - 1) * d.ldaux + d.N) * 4))
                   : make_rsrc(d.C, 0);
   // Adam: param, exp_avg, exp_avg_sq, target; otherwise x0 = the bias or the ReLU-mask
   // source (a level has one or the other: validate())
@@ -1065,6 +1203,8 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   float4 q0[EPG], q1[EPG], q2[EPG], q3[EPG];
   float x0[ADAM ? 1 : NS], x1[1], x2[1], x3[1];
   RowsRegs rows_x{};
+  Rows2Regs rows2_x{};
+  static_assert(!AXA || (EPT == 1 && TMW * 4 * 8 <= NTH), "rows2_*: one epilogue row per thread, 8 lanes per (row, slot)");
   // the epilogue operands (Adam state, or the bias / mask) go out under the MFMAs; the
   // fc3 dot weights of the tile go to LDS; an axk-1 level runs its row prologue
   // the fc3 dot weight of this thread's tile column, loaded up front (buffer op with a
@@ -1086,7 +1226,8 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
     // axk 1: the row prologue's loads.  Issued here, behind the operand burst, and
     // consumed after the MFMAs: anything in flight at the k-loop header is waited for by
     // the back-edge's conservative vmcnt on the first iteration.
-    if constexpr (AXK == 1) rows_load<TMW, NTH>(batch.rows, d, m0, rows_x);   // unconditional
+    if constexpr (AXA) rows2_load<TMW, TN>(batch.rows, m0, rows2_x);
+    else if constexpr (AXK == 1) rows_load<TMW, NTH>(batch.rows, d, m0, rows_x);   // unconditional
     if constexpr (PA) {   // zero-length range where the level has no partials
       const rsrc_t rPW = make_rsrc(has_pa ? d.pa_w : d.C,
                                    has_pa ? (uint32_t)(((size_t)(d.N - 1) * d.pa_ld + d.pa_A) * 4) : 0u);
@@ -1097,7 +1238,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
         paw_x[q] = buf_ld(rPW, okw ? (uint32_t)((n0 + c) * d.pa_ld + j) * 4u : 0xfffffff0u);
       }
     }
-    {   // buffer ops with a zero-length range where the level has no dots: no branch
+    if constexpr (!AXA) {   // buffer ops with a zero-length range where the level has no dots: no branch
       const rsrc_t rDW = make_rsrc(d.dotp ? d.dotw : d.C, d.dotp ? (uint32_t)(d.N + 1) * 4u : 0u);
       const int nn = n0 + (tid < TN ? tid : 0);
       dotw_x = buf_ld(rDW, (uint32_t)(nn < d.N ? nn : 0) * 4u);
@@ -1122,12 +1263,12 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
       x3[0] = buf_ld(rT, o);
     }
 #pragma unroll
-    for (int s = 0; s < (ADAM ? 0 : NS); ++s) {
+    for (int s = 0; s < (ADAM ? 0 : AXA ? EPT : NS); ++s) {
       int row, col, n;
       const bool ok = slot(s, row, col, n);
       {
         const uint32_t o = !ok ? kOob
-                         : d.bias ? (uint32_t)(n * d.bias_ld) * 4u
+                         : !AXA && d.bias ? (uint32_t)(n * d.bias_ld) * 4u
                                   : (uint32_t)((m0 + row) * d.ldaux + n) * 4u;
         x0[s] = buf_ld(rX, o);
       }
@@ -1137,7 +1278,9 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   gemm_core<TM, TN, KSPLIT, G, MG, AXK, BF16>(d, m0, n0, red, rsum, rowsum, pre);
   SACMI_PHASE(batch.tl, 2);
   SACMI_PHASE_LAST(batch.tl, 7);
-  if (d.dotp && tid < TN) s_dotw[tid] = n0 + tid < d.N ? dotw_x : 0.f;
+  if constexpr (!AXA) {
+    if (d.dotp && tid < TN) s_dotw[tid] = n0 + tid < d.N ? dotw_x : 0.f;
+  }
   if constexpr (PA) {
     if (has_pa) {
 #pragma unroll
@@ -1153,7 +1296,28 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
       rows_finish<TMW, NTH>(batch.rows, d, m0, p == 0 && n0 == 0, bid == 0, rows_x,
                             s_q, s_coef, s_l);
   }
+  if constexpr (AXA) rows2_sum<TMW>(batch.rows, m0, bid == 0, rows2_x, s_q);
   __syncthreads();
+  // AXK 2: this thread's row coefficients, from the head sums the barrier published; the
+  // row's first thread of the writer workgroup stores them and stages the loss terms
+  float ax_coef = 0.f;
+  const bool rows_writer = p == 0 && n0 == 0;
+  if constexpr (AXA) {
+    SACMI_STAMP(36);
+    const RowsFuse& rf = batch.rows;
+    const int row = tid / TN, b = m0 + row;
+    float c0, c1, l0, l1;
+    rows2_coef(rf, b, s_q[row], rows2_x, c0, c1, l0, l1);
+    ax_coef = d.ax_slot ? c1 : c0;
+    if (rows_writer && tid % TN == 0) {
+      if (b < rf.B) {
+        if (rf.dq) { rf.dq[b] = c0; rf.dq[rf.B + b] = c1; }
+        if (rf.dq4) { rf.dq4[(size_t)b * 4] = c0; rf.dq4[((size_t)rf.B + b) * 4] = c1; }
+      }
+      s_l[row][0] = l0; s_l[row][1] = l1;
+    }
+    SACMI_STAMP(35);
+  }
   if (threadIdx.x < 64) SACMI_STAMP(32);
   SACMI_PHASE(batch.tl, 3);
   const float omb1 = 1.f - af.beta1, omb2 = 1.f - af.beta2, omtau = 1.f - af.tau;
@@ -1199,7 +1363,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
     }
   }
 #pragma unroll
-  for (int s = ADAM ? EPT : 0; s < NS; ++s) {
+  for (int s = ADAM ? EPT : 0; s < (AXA ? EPT : NS); ++s) {
     int row, col, n;
     const bool ok = slot(s, row, col, n) && !void_st;
     float v = 0.f;
@@ -1216,6 +1380,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
       if constexpr (AXK == 1) {
         if (d.axk == 1) v *= s_coef[d.ax_slot][row];   // dh = coef[b] * (u W2)
       }
+      if constexpr (AXA) v *= ax_coef;
       if constexpr (ADAM) {   // (the rowsum slot)
         adam_elem(x0[0], x1[0], x2[0], v, omb1, af.beta2, omb2, af.eps, k_ad);
         if (af.G) buf_st_pol(rG, o, v, wt);
@@ -1226,6 +1391,9 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
           buf_st_pol(rT, o, tn, wt);
           if (af.Th) st_pol(af.Th + abase - af.t_base + (o >> 2), bf16_bits(tn), wt);
         }
+      } else if constexpr (AXA) {
+        v = x0[s] > 0.f ? v : 0.f;
+        buf_st_pol(rC, o, v, wt);
       } else {
         if (d.bias) v += x0[s];
         if (d.epi == EPI_RELU) v = v <= 0.f ? 0.f : v;   // F.relu: NaN stays NaN
@@ -1233,7 +1401,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
         buf_st_pol(rC, o, v, wt);
       }
     }
-    if constexpr (!ADAM) {
+    if constexpr (!ADAM && !AXA) {
       // fc3 dot partial of this row over its 32-column block: the 32 lanes of a half
       // wave hold one row's 32 consecutive columns (TN = 32 or 64, row-major slots)
       if (s < EPT && d.dotp) {
@@ -1253,6 +1421,15 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   if constexpr (AXK == 1) {
     if (d.axk == 1) rows_loss<TMW>(batch.rows, m0, p == 0 && n0 == 0, s_l);
   }
+  if constexpr (AXA) {
+    // the loss terms were staged by one thread per row: the writer workgroups (one per row
+    // block) take a barrier of their own at the tail, where nothing else waits (a level
+    // with dL/da partials shares the barrier below)
+    if (rows_writer && !has_pa) {
+      __syncthreads();
+      rows_loss<TMW>(batch.rows, m0, true, s_l);
+    }
+  }
   if constexpr (PA) {
     if (has_pa) {
       // dL/da partial of every row over each 32-column block of this tile:
@@ -1261,6 +1438,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
       const float* s_t = s_pa;
       const float* s_w = s_pa + TMW * (TN + 1);
       __syncthreads();
+      if constexpr (AXA) rows_loss<TMW>(batch.rows, m0, rows_writer, s_l);
       const int A = d.pa_A;
       constexpr int NSB = TN / 32;
       for (int e = tid; e < TMW * NSB * A; e += NTH) {
@@ -3053,6 +3231,17 @@ static void launch_fwd_x6(GemmBatch& b, int, hipStream_t s) {
   HIP_LAUNCH_CHECK();
 }
 
+// whether every desc of the level is a plain dh desc with the A transform (k_gemm AXK 2):
+// axk 1, ReLU-mask epilogue, no bias, no bias-gradient column, no dot partials
+static bool axk_level_static(const GemmBatch& b) {
+  if (b.rows.kind != 1 && b.rows.kind != 2) return false;
+  for (int i = 0; i < b.count; ++i) {
+    const GemmDesc& d = b.d[i];
+    if (d.axk != 1 || d.epi != EPI_MASK || d.bias || d.rs_col >= 0 || d.dotp || d.a_ksc) return false;
+  }
+  return true;
+}
+
 void launch_gemm(const GemmBatch& b0, hipStream_t s) {
   if (b0.count == 0) return;
   // the batch-4096-class kernels, in this order: the first whose probe takes the level
@@ -3120,8 +3309,12 @@ void launch_gemm(const GemmBatch& b0, hipStream_t s) {
     else if (!extra) launch_k<32, 64, 4, 1, 2, false, 0>(b, g, s);
     else launch_k<32, 64, 8, 1, 2, false, 0>(b, g, s);
   } else if (axk == 1) {
-    // dh1 / dha1 with the fc3 backward folded in (A transform, coefficient in the epilogue)
-    launch_k<32, 32, 16, 2, 1, false, 1>(b, assign_tiles<32, 32>(b) + extra, s);
+    // dh1 / dha1 with the fc3 backward folded in (A transform, coefficient in the epilogue);
+    // a level of nothing but such descs (every one the update builds) runs the instantiation
+    // that compiles that path alone
+    const int g = assign_tiles<32, 32>(b) + extra;
+    if (axk_level_static(b)) launch_k<32, 32, 16, 2, 1, false, 2>(b, g, s);
+    else launch_k<32, 32, 16, 2, 1, false, 1>(b, g, s);
   } else if (t64 >= 192) {
     // widest tile that still gives one workgroup to most CUs
     launch_k<32, 64, 16, 2, 1, false, 0>(b, b.total_tiles + extra, s);
@@ -3543,8 +3736,8 @@ bool gemm_level_on_axk16(const GemmBatch& b0) {
 }
 
 // launch_gemm's own kernel choice for an axk-1 level, asked ahead of its launch: true when
-// it runs on the one-wave-group k_gemm tiles (<32, 32, 16, 2, 1, false, 1>: MG == 1, AXK ==
-// 1), the only form that computes dL/da partials.  Mirrors launch_gemm's order: the split-K
+// it runs on the one-wave-group k_gemm tiles (<32, 32, 16, 2, 1, false, 1 or 2>: MG == 1, AXK
+// >= 1), the only form that computes dL/da partials.  Mirrors launch_gemm's order: the split-K
 // and the bf16 forward kernels never take an axk level; k_axk16 (bf16, batch-4096 class);
 // then the 64-row-tile branch (more than 512 32x64 tiles, e.g. batch 1024 with hidden > 512)
 bool gemm_level_pa_capable(const GemmBatch& b0) {
