@@ -375,24 +375,23 @@ __device__ __forceinline__ void place_tile(const GemmDesc& d, int t, int& tr, in
   }
 }
 
-// layout dispatch (wave-uniform, once per workgroup)
-// AXK: whether this kernel instantiation carries the A-transform path (launch_gemm picks
-// the variant from the level's descs): 1 -> axk 1 descs among others, 0 -> none, 2 -> every
-// desc is a plain axk 1 dh desc (axk_level_static): the one core that runs, nothing else.
-template <int TM, int TN, int KSPLIT, int G, int MG, int AXK, bool BF16, class Pre>
+// The A transform and its row prologue are a property of the LEVEL (rows_level, on the
+// host): no desc has it, or every desc is a plain dh desc with it behind a critic or actor
+// prologue.  Device code never tests GemmDesc::axk.  ROWS: which, and the prologue's form:
+//   kRowsNone    no transform: the operand layouts are dispatched below
+//   kRowsTile64  64-row two-wave-group tiles: rows_load / rows_finish (as k_axk16, k_axk_x6)
+//   kRowsSpread  32x32 one-wave-group tiles: rows2_load / rows2_sum, the coefficients per
+//                epilogue thread, the dL/da partials (it needs TMW * 4 * 8 <= threads)
+// A row-prologue level has the one core: fc3 backward folded into dh1 / dha1 (A = h2
+// transformed, B = W2).  (Layout dispatch: wave-uniform, once per workgroup.)
+constexpr int kRowsNone = 0, kRowsTile64 = 1, kRowsSpread = 2;
+template <int TM, int TN, int KSPLIT, int G, int MG, int ROWS, bool BF16, class Pre>
 __device__ __forceinline__ void gemm_core(const GemmDesc& d, int m0, int n0, float* red,
                                           float* rsum, bool rowsum, Pre&& pre) {
-  if constexpr (AXK == 2) {
+  if constexpr (ROWS != kRowsNone) {
     gemm_core_l<TM, TN, KSPLIT, G, true, false, false, MG, 1, BF16>(d, m0, n0, red, rsum, pre,
                                                                   n0 == 0 && d.ax_out != nullptr);
     return;
-  }
-  if constexpr (AXK == 1) {
-    if (d.axk == 1) {   // fc3 backward folded into dh1 / dha1 (A = h2, B = W2)
-      gemm_core_l<TM, TN, KSPLIT, G, true, false, false, MG, 1, BF16>(d, m0, n0, red, rsum, pre,
-                                                                    n0 == 0 && d.ax_out != nullptr);
-      return;
-    }
   }
   if (d.a_kc) {
     if (d.b_kc) gemm_core_l<TM, TN, KSPLIT, G, true, true, false, MG, 0, BF16>(d, m0, n0, red, rsum, pre);
@@ -598,8 +597,8 @@ __device__ __forceinline__ void polyak_ride(const PolyakArgs& a, int w, int nw) 
 // One workgroup (16 waves, K split 16 ways) per output tile, one workgroup per CU.
 // Block 0 of an Adam-fused level also finalises the losses, takes the scalar
 // log_alpha step (alpha = exp(log_alpha), sac_imp.py:128-135) and fills the loss ring.
-// Row prologue of an axk-1 level (runs inside pre(), i.e. while the operand loads are in
-// flight): four threads per batch row sum the dot partials of its heads, the row's
+// Row prologue of a dh1 level with the A transform (runs inside pre(), i.e. while the operand
+// loads are in flight): four threads per batch row sum the dot partials of its heads, the row's
 // thread loads r, d, logp meanwhile and turns the heads into the per-row coefficients
 // of the backward —
 //   critic (sac_imp.py:87-113): q^ = r + (1-d) gamma (min(qt1,qt2) - alpha logp'),
@@ -621,21 +620,19 @@ struct RowsRegs {
 };
 
 template <int TMW, int NTH>
-__device__ __forceinline__ void rows_load(const RowsFuse& rf, const GemmDesc& d, int m0,
-                                          RowsRegs& x) {
+__device__ __forceinline__ void rows_load(const RowsFuse& rf, int m0, RowsRegs& x) {
   const int t = threadIdx.x;
   const int nslot = rf.kind == 1 ? 4 : 2;
-  // unconditional buffer loads (a guarded load is drained at the end of its guard);
-  // descriptors of zero length where this desc has no prologue (nothing is read), and
-  // reads past a range for the threads / parts that have none (they return 0)
-  const bool on = d.axk == 1;
+  // unconditional buffer loads (a guarded load is drained at the end of its guard): reads
+  // past a range for the threads / parts that have none (they return 0), a zero-length
+  // descriptor where the level has no logp_part
   const uint32_t big = 0x7fffffffu, oob = 0xfffffff0u;
-  const rsrc_t rPart = make_rsrc(on ? rf.part : d.C, on ? big : 0u);
-  const rsrc_t rLp = make_rsrc(on ? rf.logp : d.C, on ? big : 0u);
-  const rsrc_t rR = make_rsrc(on ? (rf.kind == 1 ? rf.r : rf.logp) : d.C, on ? big : 0u);
-  const rsrc_t rD = make_rsrc(on ? (rf.kind == 1 ? rf.d : rf.logp) : d.C, on ? big : 0u);
-  const rsrc_t rLpa = make_rsrc(on && rf.logp_part ? rf.logp_part : d.C, on && rf.logp_part ? big : 0u);
-  const rsrc_t rSc = make_rsrc(on ? &rf.sc->alpha : d.C, on ? 4u : 0u);
+  const rsrc_t rPart = make_rsrc(rf.part, big);
+  const rsrc_t rLp = make_rsrc(rf.logp, big);
+  const rsrc_t rR = make_rsrc(rf.kind == 1 ? rf.r : rf.logp, big);
+  const rsrc_t rD = make_rsrc(rf.kind == 1 ? rf.d : rf.logp, big);
+  const rsrc_t rLpa = make_rsrc(rf.logp_part ? rf.logp_part : rf.logp, rf.logp_part ? big : 0u);
+  const rsrc_t rSc = make_rsrc(&rf.sc->alpha, 4u);
   {
     const int row = t / nslot, sl = t % nslot;
     const bool ok = t < TMW * nslot && m0 + row < rf.B;
@@ -654,8 +651,69 @@ __device__ __forceinline__ void rows_load(const RowsFuse& rf, const GemmDesc& d,
   x.lpa = buf_ld(rLpa, (uint32_t)(2 * (lane >= 0 && lane < rf.n_lp ? lane : 0) + 1) * 4u);
 }
 
+// The coefficients (c0, c1) and loss terms (l0, l1) of batch row b from its head sums
+// q[0..3]: the one text of this arithmetic (rows_finish and k_gemm's spread form call it),
+// so the losses and dq bits do not depend on the kernel.
+template <class Regs>   // RowsRegs or Rows2Regs: the row's alpha, lp, r, d
+__device__ __forceinline__ void rows_coef(const RowsFuse& rf, int b, const float* q, const Regs& x,
+                                          float& c0, float& c1, float& l0, float& l1) {
+  c0 = 0.f; c1 = 0.f; l0 = 0.f; l1 = 0.f;
+  if (b < rf.B) {
+    if (rf.kind == 1) {
+      const float vt = fminf(q[2], q[3]) - x.alpha * x.lp;
+      const float qhat = x.r + ((1.f - x.d) * rf.gamma) * vt;
+      const float e1 = q[0] - qhat, e2 = q[1] - qhat;
+      c0 = 2.f * e1 / (float)rf.B;
+      c1 = 2.f * e2 / (float)rf.B;
+      l0 = e1 * e1;
+      l1 = e2 * e2;
+    } else {
+      const float q1 = q[0], q2 = q[1];
+      l0 = x.alpha * x.lp - fminf(q1, q2);
+      const float g = -1.f / (float)rf.B;
+      const float w1 = q1 < q2 ? 1.f : (q1 == q2 ? 0.5f : 0.f);
+      c0 = g * w1;
+      c1 = g * (1.f - w1);
+    }
+  }
+}
+
+// Block 0 of an actor level, the first wave past the partial-sum threads (`lane` of it,
+// lpa = logp_part[2 * lane + 1] where lane < n_lp): dL/dlog_alpha and the step counters
+// (both forms of the prologue call it).
+__device__ __forceinline__ void rows_actor_block0(const RowsFuse& rf, int lane, float lpa) {
+  // dL/dlog_alpha = -mean(logp_a + te) (sac_imp.py:128-133) from the heads kernel's
+  // per-workgroup sums: strided per lane, then a fixed butterfly
+  float acc = 0.f;
+  if (rf.alpha_grad) {
+    if (lane < rf.n_lp) acc += lpa;
+    for (int w = lane + 64; w < rf.n_lp; w += 64) acc += rf.logp_part[2 * w + 1];
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if (lane == 0) {
+    if (rf.alpha_grad) *rf.alpha_grad = -(acc + (float)rf.B * rf.target_entropy) / (float)rf.B;
+    // step counters: the critic Adam ran before this level, the actor Adam after.  After
+    // a non-finite policy sample (ErrBits) only the steps the reference took advance —
+    // none (target batch / PER / an earlier update), or the critics' (actor batch,
+    // sac_imp.py:116 raises after the q optimizers stepped) — selected, not branched:
+    // every load goes out at once
+    const int err = rf.sc->err;
+    const bool any = (err & kErrSkipAll) == 0;
+    const bool all = any && (err & kErrActLike) == 0;
+    for (int i = 0; i < 4; ++i) {
+      const bool adv = all || (any && (i == 1 || i == 2));
+      rf.sc->step[i] += adv ? 1.0 : 0.0;
+      rf.sc->beta_pow[i][0] *= adv ? 0.9 : 1.0;   // torch Adam default betas (sac_imp.py:39-49)
+      rf.sc->beta_pow[i][1] *= adv ? 0.999 : 1.0;
+    }
+    rf.sc->noise_counter += all ? 1 : 0;
+    if (any && !all) atomicOr(&rf.sc->err, (int)ERR_ABORT);
+  }
+}
+
 template <int TMW, int NTH>
-__device__ void rows_finish(const RowsFuse& rf, const GemmDesc& d, int m0, bool writer,
+__device__ void rows_finish(const RowsFuse& rf, int m0, bool writer,
                             bool first_block, const RowsRegs& x0,
                             float (*s_q)[4], float (*s_coef)[TMW], float (*s_l)[2]) {
   const int t = threadIdx.x;
@@ -680,60 +738,15 @@ __device__ void rows_finish(const RowsFuse& rf, const GemmDesc& d, int m0, bool 
   }
   if (first_block && rf.kind == 2) {
     const int w0 = TMW * nslot;            // first wave past the partial-sum threads
-    if (t >= w0 && t < w0 + 64) {
-      // dL/dlog_alpha = -mean(logp_a + te) (sac_imp.py:128-133) from the heads kernel's
-      // per-workgroup sums: strided per lane, then a fixed butterfly
-      const int lane = t - w0;
-      float acc = 0.f;
-      if (rf.alpha_grad) {
-        if (lane < rf.n_lp) acc += x.lpa;
-        for (int w = lane + 64; w < rf.n_lp; w += 64) acc += rf.logp_part[2 * w + 1];
-      }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-      if (lane == 0) {
-        if (rf.alpha_grad) *rf.alpha_grad = -(acc + (float)rf.B * rf.target_entropy) / (float)rf.B;
-        // step counters: the critic Adam ran before this level, the actor Adam after.  After
-        // a non-finite policy sample (ErrBits) only the steps the reference took advance —
-        // none (target batch / PER / an earlier update), or the critics' (actor batch,
-        // sac_imp.py:116 raises after the q optimizers stepped) — selected, not branched:
-        // every load goes out at once
-        const int err = rf.sc->err;
-        const bool any = (err & kErrSkipAll) == 0;
-        const bool all = any && (err & kErrActLike) == 0;
-        for (int i = 0; i < 4; ++i) {
-          const bool adv = all || (any && (i == 1 || i == 2));
-          rf.sc->step[i] += adv ? 1.0 : 0.0;
-          rf.sc->beta_pow[i][0] *= adv ? 0.9 : 1.0;   // torch Adam default betas (sac_imp.py:39-49)
-          rf.sc->beta_pow[i][1] *= adv ? 0.999 : 1.0;
-        }
-        rf.sc->noise_counter += all ? 1 : 0;
-        if (any && !all) atomicOr(&rf.sc->err, (int)ERR_ABORT);
-      }
-    }
+    if (t >= w0 && t < w0 + 64) rows_actor_block0(rf, t - w0, x.lpa);
   }
   __syncthreads();
   SACMI_STAMP(36);
   const int b = m0 + t;
   if (t < TMW) {
-    float c0 = 0.f, c1 = 0.f, l0 = 0.f, l1 = 0.f;
+    float c0, c1, l0, l1;
+    rows_coef(rf, b, s_q[t], x, c0, c1, l0, l1);
     if (b < rf.B) {
-      if (rf.kind == 1) {
-        const float vt = fminf(s_q[t][2], s_q[t][3]) - x.alpha * x.lp;
-        const float qhat = x.r + ((1.f - x.d) * rf.gamma) * vt;
-        const float e1 = s_q[t][0] - qhat, e2 = s_q[t][1] - qhat;
-        c0 = 2.f * e1 / (float)rf.B;
-        c1 = 2.f * e2 / (float)rf.B;
-        l0 = e1 * e1;
-        l1 = e2 * e2;
-      } else {
-        const float q1 = s_q[t][0], q2 = s_q[t][1];
-        l0 = x.alpha * x.lp - fminf(q1, q2);
-        const float g = -1.f / (float)rf.B;
-        const float w1 = q1 < q2 ? 1.f : (q1 == q2 ? 0.5f : 0.f);
-        c0 = g * w1;
-        c1 = g * (1.f - w1);
-      }
       if (writer && rf.dq) { rf.dq[b] = c0; rf.dq[rf.B + b] = c1; }
       if (writer && rf.dq4) { rf.dq4[(size_t)b * 4] = c0; rf.dq4[((size_t)rf.B + b) * 4] = c1; }
     }
@@ -761,8 +774,8 @@ __device__ __forceinline__ void rows_loss(const RowsFuse& rf, int m0, bool write
   }
 }
 
-// The row prologue of a level whose every desc is axk 1 (k_gemm AXK 2), same values as
-// rows_load / rows_finish in far fewer registers and one barrier:
+// The spread form of the row prologue (k_gemm kRowsSpread), same values as rows_load /
+// rows_finish in far fewer registers and one barrier:
 //  * the TMW * nslot * 16 dot partials are spread over the whole workgroup, two per thread
 //    (eight lanes per (row, slot): lane j holds partials j and j + 8), and summed in
 //    column order inside the wave that loaded them, by lane shuffles — no thread carries
@@ -806,7 +819,7 @@ __device__ __forceinline__ void rows2_load(const RowsFuse& rf, int m0, Rows2Regs
 }
 
 // after the MFMAs, before the workgroup's barrier: the head sums to s_q, and block 0 of
-// an actor level its scalar work (as in rows_finish)
+// an actor level its scalar work
 template <int TMW>
 __device__ __forceinline__ void rows2_sum(const RowsFuse& rf, int m0, bool first_block, Rows2Regs& x,
                                           float (*s_q)[4]) {
@@ -836,56 +849,7 @@ __device__ __forceinline__ void rows2_sum(const RowsFuse& rf, int m0, bool first
   }
   if (first_block && rf.kind == 2) {
     const int w0 = TMW * nslot;            // first wave past the partial-sum threads
-    if (t >= w0 && t < w0 + 64) {
-      // dL/dlog_alpha and the step counters: rows_finish's block, unchanged
-      const int lane = t - w0;
-      float acc = 0.f;
-      if (rf.alpha_grad) {
-        if (lane < rf.n_lp) acc += x.lpa;
-        for (int w = lane + 64; w < rf.n_lp; w += 64) acc += rf.logp_part[2 * w + 1];
-      }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-      if (lane == 0) {
-        if (rf.alpha_grad) *rf.alpha_grad = -(acc + (float)rf.B * rf.target_entropy) / (float)rf.B;
-        const int err = rf.sc->err;
-        const bool any = (err & kErrSkipAll) == 0;
-        const bool all = any && (err & kErrActLike) == 0;
-        for (int i = 0; i < 4; ++i) {
-          const bool adv = all || (any && (i == 1 || i == 2));
-          rf.sc->step[i] += adv ? 1.0 : 0.0;
-          rf.sc->beta_pow[i][0] *= adv ? 0.9 : 1.0;   // torch Adam default betas (sac_imp.py:39-49)
-          rf.sc->beta_pow[i][1] *= adv ? 0.999 : 1.0;
-        }
-        rf.sc->noise_counter += all ? 1 : 0;
-        if (any && !all) atomicOr(&rf.sc->err, (int)ERR_ABORT);
-      }
-    }
-  }
-}
-
-// after the barrier: the coefficients (c0, c1) and loss terms of batch row b from its head
-// sums q[0..3] — rows_finish's arithmetic, expression for expression
-__device__ __forceinline__ void rows2_coef(const RowsFuse& rf, int b, const float* q, const Rows2Regs& x,
-                                           float& c0, float& c1, float& l0, float& l1) {
-  c0 = 0.f; c1 = 0.f; l0 = 0.f; l1 = 0.f;
-  if (b < rf.B) {
-    if (rf.kind == 1) {
-      const float vt = fminf(q[2], q[3]) - x.alpha * x.lp;
-      const float qhat = x.r + ((1.f - x.d) * rf.gamma) * vt;
-      const float e1 = q[0] - qhat, e2 = q[1] - qhat;
-      c0 = 2.f * e1 / (float)rf.B;
-      c1 = 2.f * e2 / (float)rf.B;
-      l0 = e1 * e1;
-      l1 = e2 * e2;
-    } else {
-      const float q1 = q[0], q2 = q[1];
-      l0 = x.alpha * x.lp - fminf(q1, q2);
-      const float g = -1.f / (float)rf.B;
-      const float w1 = q1 < q2 ? 1.f : (q1 == q2 ? 0.5f : 0.f);
-      c0 = g * w1;
-      c1 = g * (1.f - w1);
-    }
+    if (t >= w0 && t < w0 + 64) rows_actor_block0(rf, t - w0, x.lpa);
   }
 }
 
@@ -1016,10 +980,10 @@ __device__ __forceinline__ void heads_logp(const HeadSampleArgs& a, int m0, int 
 template <int KSPLIT, int MG>
 constexpr int gemm_threads() { return 64 * KSPLIT * MG; }
 // LDS of one k_gemm configuration (kg_body)
-template <int TM, int TN, int KSPLIT, int MG, int AXK>
+template <int TM, int TN, int KSPLIT, int MG, int ROWS>
 struct KgSmem {
   static constexpr int TMW = TM * MG;
-  static constexpr bool PA = AXK >= 1 && MG == 1;
+  static constexpr bool PA = ROWS == kRowsSpread;
   float red[MG * KSPLIT * TM * (TN + 1)];
   float rsum[MG * KSPLIT * TM];
   AdamScalars s_k;
@@ -1029,16 +993,27 @@ struct KgSmem {
 };
 
 // The body of one k_gemm workgroup: work item `bid` of the level (a tile, a ride-along
-// workgroup, the scalar Adam workgroup).
-// The scalars that locate this workgroup's work come in ONE kernarg round trip: left to
-// the compiler, each load sat behind a branch on the previous one (timeline pointer, tile
-// count, one desc's tile_begin per loop trip, then the desc's fields as they were used),
-// ~1-1.5 us of dependent scalar round trips before the first operand load of every level
-// (phase stamps, tools/phase_dump.py).  The asm pins force each value into an SGPR
-// there, so every load is issued before the one wait.
-template <int TM, int TN, int KSPLIT, int G, int MG, bool ADAM, int AXK, bool BF16>
+// workgroup, the scalar Adam workgroup).  Its pieces, in order (the ---- marks): locating
+// the work; prefetching the epilogue's operands (pre(), which gemm_core_l runs behind the
+// operand burst); the K loop; the staging and row-prologue half after the MFMAs; ONE of
+// three epilogues — fused Adam, dh (a row-prologue level) or plain; the loss partial and
+// the dL/da tail.  The pieces stay in this one function: cut out as functions or lambdas
+// they changed the ISA of every k_gemm instantiation.
+template <int TM, int TN, int KSPLIT, int G, int MG, bool ADAM, int ROWS, bool BF16>
 __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
-                                        KgSmem<TM, TN, KSPLIT, MG, AXK>& sm) {
+                                        KgSmem<TM, TN, KSPLIT, MG, ROWS>& sm) {
+  // AX: a row-prologue level (every desc a plain dh desc with the A transform); SPREAD: its
+  // 32x32 one-wave-group form, which also forms the dL/da partials (PA)
+  constexpr bool AX = ROWS != kRowsNone, SPREAD = ROWS == kRowsSpread, PA = SPREAD;
+  static_assert(!AX || !ADAM, "a row-prologue level has no fused Adam");
+  static_assert(!SPREAD || MG == 1, "the spread prologue: one wave group");
+  // ---- locating the work: the scalar pins, the ride-along workgroups, the desc, the tile.
+  // The scalars that locate this workgroup's work come in ONE kernarg round trip: left to
+  // the compiler, each load sat behind a branch on the previous one (timeline pointer, tile
+  // count, one desc's tile_begin per loop trip, then the desc's fields as they were used),
+  // ~1-1.5 us of dependent scalar round trips before the first operand load of every level
+  // (phase stamps, tools/phase_dump.py).  The asm pins force each value into an SGPR
+  // there, so every load is issued before the one wait.
   tl_word* const tl = batch.tl;
   const int n_tiles = batch.total_tiles, n_desc = batch.count;
   int tbeg[kMaxGemms];
@@ -1049,7 +1024,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   for (int q = 0; q < kMaxGemms; ++q) asm volatile("" :: "s"(tbeg[q]));
   // ... with the level-wide epilogue scalars that do not depend on the desc (the row
   // prologue's / fused Adam's pointers): otherwise their loads sit behind the desc's
-  if constexpr (AXK >= 1) {
+  if constexpr (AX) {
     const RowsFuse& r = batch.rows;
     asm volatile("" :: "s"(r.part), "s"(r.logp), "s"(r.r), "s"(r.d), "s"(r.kind), "s"(r.nparts),
                  "s"(r.B), "s"(r.sc), "s"(r.logp_part), "s"(r.n_lp));
@@ -1069,9 +1044,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   auto& s_coef = sm.s_coef;
   auto& s_l = sm.s_l;
   auto& s_dotw = sm.s_dotw;
-  // dL/da partials (axk-1 levels of one 32-row wave group): the tile's outputs [TMW][TN+1]
-  // and its fc1 action weights [TN][32]
-  constexpr bool PA = AXK >= 1 && MG == 1;
+  // dL/da partials (PA): the tile's outputs [TMW][TN+1] and its fc1 action weights [TN][32]
   float* const s_pa = sm.s_pa;
   if (bid >= n_tiles) {   // ride-along workgroups (next update's replay work, Polyak)
     if constexpr (gemm_threads<KSPLIT, MG>() == 1024) {   // the host attaches rides to 1024-thread configs
@@ -1103,7 +1076,8 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   // ... and, in the same round trip (one asm statement: every load issued before the one
   // wait), the fields the epilogue's buffer descriptors and scalars are formed from — the
   // compiler forms them before the K loop, behind branches on the fields: two or three more
-  // dependent round trips before the first operand load otherwise (ISA)
+  // dependent round trips before the first operand load otherwise (ISA).  (d.axk rides in
+  // the same load; nothing tests it)
 #define SACMI_DESC_PIN_E "s"(d.C), "s"(d.aux), "s"(d.ldc), "s"(d.ldaux), "s"(d.epi), "s"(d.bias), \
     "s"(d.bias_ld), "s"(d.dotw), "s"(d.dotp), "s"(d.rs_col), "s"(d.axk), "s"(d.ax_w), "s"(d.ax_out), \
     "s"(d.ax_ld), "s"(d.a_ksc)
@@ -1112,7 +1086,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
     asm volatile("" :: SACMI_DESC_PIN_K, SACMI_DESC_PIN_E, "s"(a.P), "s"(a.M), "s"(a.V), "s"(a.T),
                  "s"(a.G), "s"(a.t_base), "s"(a.lr), "s"(a.beta1), "s"(a.beta2), "s"(a.eps),
                  "s"(a.tau), "s"(a.step_offset), "s"(a.sc), "s"(d.adam_step));
-  } else if constexpr (AXK >= 1) {
+  } else if constexpr (AX) {
     const RowsFuse& r = batch.rows;
     asm volatile("" :: SACMI_DESC_PIN_K, SACMI_DESC_PIN_E, "s"(d.pa_w), "s"(d.pa_out), "s"(d.pa_ld),
                  "s"(d.pa_A), "s"(d.pa_base), "s"(r.part), "s"(r.logp), "s"(r.r), "s"(r.d),
@@ -1138,15 +1112,8 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
                        1.f - a.beta2);
     }
   }
-  // AXK 2: every desc is a plain dh desc (axk 1, mask epilogue, no bias, no bias-gradient
-  // column, no dot partials: axk_level_static) — what the other forms select at run time,
-  // and build a zero-length descriptor for, is not compiled at all
-  constexpr bool AXA = AXK == 2;
-  const bool rowsum = !AXA && d.rs_col >= 0 && n0 == 0;
+  const bool rowsum = !AX && d.rs_col >= 0 && n0 == 0;
   const AdamFuse& af = batch.adam;
-  // Adam bias corrections and the error bits: thread 0 reads them in pre(), behind its
-  // wave's operand loads (at the kernel's start they put a device-memory round trip in
-  // front of wave 0's operand loads), into LDS for the epilogue
   // Element slots: EPT tile outputs per thread (e = tid + s*NTH) plus one slot for the
   // rowsum (bias-gradient) column.  Their epilogue operands (bias, ReLU mask, Adam
   // state) are loaded by pre() while the MFMAs run.
@@ -1173,7 +1140,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   // byte span of this desc's output (tile rows, plus the rowsum column; the fused-Adam
   // 4-column groups reach the row's padding up to a multiple of 4: ldc is one)
   const int ncov = ADAM ? (d.N + 3) & ~3 : d.N;
-  const uint32_t span = (uint32_t)(((size_t)(d.M - 1) * d.ldc + (!AXA && d.rs_col >= ncov ? d.rs_col + 1 : ncov)) * 4);
+  const uint32_t span = (uint32_t)(((size_t)(d.M - 1) * d.ldc + (!AX && d.rs_col >= ncov ? d.rs_col + 1 : ncov)) * 4);
   const size_t abase = ADAM ? (size_t)(d.C - af.P) : 0;
   const rsrc_t rC = make_rsrc(d.C, span);
   // (unused descriptors get a zero-length range: any access through them is dropped)
@@ -1181,8 +1148,8 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   const rsrc_t rV = make_rsrc(ADAM ? af.V + abase : d.C, ADAM ? span : 0);
   const rsrc_t rT = make_rsrc(ADAM && pol ? af.T + abase - af.t_base : d.C, ADAM && pol ? span : 0);
   const rsrc_t rG = make_rsrc(ADAM && af.G ? af.G + abase : d.C, ADAM && af.G ? span : 0);
-  const rsrc_t rX = !AXA && d.bias ? make_rsrc(d.bias, (uint32_t)(((size_t)(d.N - 1) * d.bias_ld + 1) * 4))
-                  : AXA || d.epi == EPI_MASK ? make_rsrc(d.aux, (uint32_t)(((size_t)(d.M - 1) * d.ldaux + d.N) * 4))
+  const rsrc_t rX = !AX && d.bias ? make_rsrc(d.bias, (uint32_t)(((size_t)(d.N - 1) * d.bias_ld + 1) * 4))
+                  : AX || d.epi == EPI_MASK ? make_rsrc(d.aux, (uint32_t)(((size_t)(d.M - 1) * d.ldaux + d.N) * 4))
                   : make_rsrc(d.C, 0);
   // Adam: param, exp_avg, exp_avg_sq, target; otherwise x0 = the bias or the ReLU-mask
   // source (a level has one or the other: validate())
@@ -1204,30 +1171,32 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   float x0[ADAM ? 1 : NS], x1[1], x2[1], x3[1];
   RowsRegs rows_x{};
   Rows2Regs rows2_x{};
-  static_assert(!AXA || (EPT == 1 && TMW * 4 * 8 <= NTH), "rows2_*: one epilogue row per thread, 8 lanes per (row, slot)");
-  // the epilogue operands (Adam state, or the bias / mask) go out under the MFMAs; the
-  // fc3 dot weights of the tile go to LDS; an axk-1 level runs its row prologue
-  // the fc3 dot weight of this thread's tile column, loaded up front (buffer op with a
-  // zero-length range where the level has none: no branch, so nothing waits for it early)
-  // (loaded in pre(), after the operand burst; staged to LDS after the MFMAs)
+  static_assert(!SPREAD || (EPT == 1 && TMW * 4 * 8 <= NTH), "rows2_*: one epilogue row per thread, 8 lanes per (row, slot)");
+  // the fc3 dot weight of this thread's tile column and the head's bias (plain levels:
+  // loaded in pre(), staged to LDS after the MFMAs)
   float dotw_x = 0.f, dotb_x = 0.f;
-  // dL/da partials (GemmDesc::pa_out, axk-1 levels only): this tile's columns of the fc1
+  // dL/da partials (GemmDesc::pa_out, the spread form only): this tile's columns of the fc1
   // action weights, loaded under the MFMAs, staged [TN][32] in LDS after them
   constexpr int PW = PA ? (TN * 32 + NTH - 1) / NTH : 1;
   float paw_x[PW];
   const bool has_pa = PA && d.pa_out != nullptr;
+  // ---- prefetching the epilogue's operands behind the operand burst: the Adam state or the
+  // bias / mask source, the row prologue's loads, the dot and dL/da weights
   auto pre = [&]() {
+    // Adam bias corrections and the error bits: thread 0 reads them here, behind its wave's
+    // operand loads (at the kernel's start they put a device-memory round trip in front of
+    // wave 0's operand loads), into LDS for the epilogue
     if constexpr (ADAM) {
       if (threadIdx.x == 0) {
         s_k = fuse_scalars(af, d.adam_step, af.step_offset);
         s_err = af.sc->err;
       }
     }
-    // axk 1: the row prologue's loads.  Issued here, behind the operand burst, and
+    // the row prologue's loads.  Issued here, behind the operand burst, and
     // consumed after the MFMAs: anything in flight at the k-loop header is waited for by
     // the back-edge's conservative vmcnt on the first iteration.
-    if constexpr (AXA) rows2_load<TMW, TN>(batch.rows, m0, rows2_x);
-    else if constexpr (AXK == 1) rows_load<TMW, NTH>(batch.rows, d, m0, rows_x);   // unconditional
+    if constexpr (SPREAD) rows2_load<TMW, TN>(batch.rows, m0, rows2_x);
+    else if constexpr (AX) rows_load<TMW, NTH>(batch.rows, m0, rows_x);
     if constexpr (PA) {   // zero-length range where the level has no partials
       const rsrc_t rPW = make_rsrc(has_pa ? d.pa_w : d.C,
                                    has_pa ? (uint32_t)(((size_t)(d.N - 1) * d.pa_ld + d.pa_A) * 4) : 0u);
@@ -1238,7 +1207,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
         paw_x[q] = buf_ld(rPW, okw ? (uint32_t)((n0 + c) * d.pa_ld + j) * 4u : 0xfffffff0u);
       }
     }
-    if constexpr (!AXA) {   // buffer ops with a zero-length range where the level has no dots: no branch
+    if constexpr (!AX) {   // buffer ops with a zero-length range where the level has no dots: no branch
       const rsrc_t rDW = make_rsrc(d.dotp ? d.dotw : d.C, d.dotp ? (uint32_t)(d.N + 1) * 4u : 0u);
       const int nn = n0 + (tid < TN ? tid : 0);
       dotw_x = buf_ld(rDW, (uint32_t)(nn < d.N ? nn : 0) * 4u);
@@ -1263,22 +1232,23 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
       x3[0] = buf_ld(rT, o);
     }
 #pragma unroll
-    for (int s = 0; s < (ADAM ? 0 : AXA ? EPT : NS); ++s) {
+    for (int s = 0; s < (ADAM ? 0 : AX ? EPT : NS); ++s) {
       int row, col, n;
       const bool ok = slot(s, row, col, n);
       {
         const uint32_t o = !ok ? kOob
-                         : !AXA && d.bias ? (uint32_t)(n * d.bias_ld) * 4u
+                         : !AX && d.bias ? (uint32_t)(n * d.bias_ld) * 4u
                                   : (uint32_t)((m0 + row) * d.ldaux + n) * 4u;
         x0[s] = buf_ld(rX, o);
       }
     }
   };
   SACMI_PHASE(batch.tl, 1);
-  gemm_core<TM, TN, KSPLIT, G, MG, AXK, BF16>(d, m0, n0, red, rsum, rowsum, pre);
+  gemm_core<TM, TN, KSPLIT, G, MG, ROWS, BF16>(d, m0, n0, red, rsum, rowsum, pre);
   SACMI_PHASE(batch.tl, 2);
   SACMI_PHASE_LAST(batch.tl, 7);
-  if constexpr (!AXA) {
+  // ---- after the MFMAs: the prefetched weights to LDS, the row prologue's second half
+  if constexpr (!AX) {
     if (d.dotp && tid < TN) s_dotw[tid] = n0 + tid < d.N ? dotw_x : 0.f;
   }
   if constexpr (PA) {
@@ -1290,24 +1260,20 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
       }
     }
   }
-  if constexpr (AXK == 1) {
-    // the row prologue, after the MFMAs: its loads went out first and have long landed
-    if (d.axk == 1)
-      rows_finish<TMW, NTH>(batch.rows, d, m0, p == 0 && n0 == 0, bid == 0, rows_x,
-                            s_q, s_coef, s_l);
-  }
-  if constexpr (AXA) rows2_sum<TMW>(batch.rows, m0, bid == 0, rows2_x, s_q);
+  if constexpr (ROWS == kRowsTile64)
+    rows_finish<TMW, NTH>(batch.rows, m0, p == 0 && n0 == 0, bid == 0, rows_x, s_q, s_coef, s_l);
+  if constexpr (SPREAD) rows2_sum<TMW>(batch.rows, m0, bid == 0, rows2_x, s_q);
   __syncthreads();
-  // AXK 2: this thread's row coefficients, from the head sums the barrier published; the
+  // the spread form: this thread's row coefficients, from the head sums the barrier published; the
   // row's first thread of the writer workgroup stores them and stages the loss terms
   float ax_coef = 0.f;
   const bool rows_writer = p == 0 && n0 == 0;
-  if constexpr (AXA) {
+  if constexpr (SPREAD) {
     SACMI_STAMP(36);
     const RowsFuse& rf = batch.rows;
     const int row = tid / TN, b = m0 + row;
     float c0, c1, l0, l1;
-    rows2_coef(rf, b, s_q[row], rows2_x, c0, c1, l0, l1);
+    rows_coef(rf, b, s_q[row], rows2_x, c0, c1, l0, l1);
     ax_coef = d.ax_slot ? c1 : c0;
     if (rows_writer && tid % TN == 0) {
       if (b < rf.B) {
@@ -1328,6 +1294,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   const bool void_st = ADAM && (err & af.err_skip) != 0;
   const bool pol_st = pol && (err & af.err_nopolyak) == 0;
   if constexpr (ADAM) {
+    // ---- the fused-Adam epilogue: the tile as 4-column groups, then the rowsum slot
     // 4-column groups: the gradient of a column past N (a row pad) is taken as 0, so the
     // Adam / Polyak arithmetic leaves the pad (0) exactly 0 and the 16-byte stores rewrite it
 #pragma unroll
@@ -1361,27 +1328,16 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
         if (af.Th) st_bf4(af.Th + abase - af.t_base + (o >> 2), t);
       }
     }
-  }
 #pragma unroll
-  for (int s = ADAM ? EPT : 0; s < (AXA ? EPT : NS); ++s) {
-    int row, col, n;
-    const bool ok = slot(s, row, col, n) && !void_st;
-    float v = 0.f;
-    if (ok) {
-      if (s < EPT) {
-        v = reduce_partials<TM, TN, KSPLIT, MG>(red, row, col);
-      } else {
+    for (int s = EPT; s < NS; ++s) {   // (the rowsum slot)
+      int row, col, n;
+      const bool ok = slot(s, row, col, n) && !void_st;
+      if (ok) {
         const float* rb = rsum + (row / TM) * KSPLIT * TM + row % TM;
-        v = rb[0];
+        float v = rb[0];
 #pragma unroll
         for (int w = 1; w < KSPLIT; ++w) v += rb[w * TM];
-      }
-      const uint32_t o = (uint32_t)((m0 + row) * d.ldc + n) * 4u;
-      if constexpr (AXK == 1) {
-        if (d.axk == 1) v *= s_coef[d.ax_slot][row];   // dh = coef[b] * (u W2)
-      }
-      if constexpr (AXA) v *= ax_coef;
-      if constexpr (ADAM) {   // (the rowsum slot)
+        const uint32_t o = (uint32_t)((m0 + row) * d.ldc + n) * 4u;
         adam_elem(x0[0], x1[0], x2[0], v, omb1, af.beta2, omb2, af.eps, k_ad);
         if (af.G) buf_st_pol(rG, o, v, wt);
         buf_st_pol(rC, o, x0[0], wt); buf_st_pol(rM, o, x1[0], wt); buf_st_pol(rV, o, x2[0], wt);
@@ -1391,17 +1347,51 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
           buf_st_pol(rT, o, tn, wt);
           if (af.Th) st_pol(af.Th + abase - af.t_base + (o >> 2), bf16_bits(tn), wt);
         }
-      } else if constexpr (AXA) {
+      }
+    }
+  } else if constexpr (AX) {
+    // ---- the dh epilogue of a row-prologue level: dh = coef[b] * (u W2), masked by the layer
+    // below; the spread form stages every tile element (0 outside the output) for the dL/da tail
+#pragma unroll
+    for (int s = 0; s < EPT; ++s) {
+      int row, col, n;
+      const bool ok = slot(s, row, col, n);
+      float v = 0.f;
+      if (ok) {
+        v = reduce_partials<TM, TN, KSPLIT, MG>(red, row, col);
+        const uint32_t o = (uint32_t)((m0 + row) * d.ldc + n) * 4u;
+        if constexpr (SPREAD) v *= ax_coef;
+        else v *= s_coef[d.ax_slot][row];
         v = x0[s] > 0.f ? v : 0.f;
         buf_st_pol(rC, o, v, wt);
-      } else {
+      }
+      if constexpr (PA) {
+        if (has_pa) s_pa[row * (TN + 1) + col] = ok ? v : 0.f;
+      }
+    }
+  } else {
+    // ---- the plain epilogue: bias, ReLU / mask, store; the bias-gradient column (the last
+    // slot); the fc3 dot partials
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      int row, col, n;
+      const bool ok = slot(s, row, col, n);
+      float v = 0.f;
+      if (ok) {
+        if (s < EPT) {
+          v = reduce_partials<TM, TN, KSPLIT, MG>(red, row, col);
+        } else {
+          const float* rb = rsum + (row / TM) * KSPLIT * TM + row % TM;
+          v = rb[0];
+#pragma unroll
+          for (int w = 1; w < KSPLIT; ++w) v += rb[w * TM];
+        }
+        const uint32_t o = (uint32_t)((m0 + row) * d.ldc + n) * 4u;
         if (d.bias) v += x0[s];
         if (d.epi == EPI_RELU) v = v <= 0.f ? 0.f : v;   // F.relu: NaN stays NaN
         else if (d.epi == EPI_MASK) v = x0[s] > 0.f ? v : 0.f;
         buf_st_pol(rC, o, v, wt);
       }
-    }
-    if constexpr (!ADAM && !AXA) {
       // fc3 dot partial of this row over its 32-column block: the 32 lanes of a half
       // wave hold one row's 32 consecutive columns (TN = 32 or 64, row-major slots)
       if (s < EPT && d.dotp) {
@@ -1412,16 +1402,12 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
           st_pol(d.dotp + (size_t)(m0 + row) * d.dotp_ld + (n0 + col) / 32, n0 + col == 0 ? c + dotb_x : c, wt);
       }
     }
-    if constexpr (PA) {   // every tile element, 0 outside the output
-      if (has_pa && s < EPT) s_pa[row * (TN + 1) + col] = ok ? v : 0.f;
-    }
   }
   if (threadIdx.x < 64) SACMI_STAMP(33);
   SACMI_PHASE(batch.tl, 4);
-  if constexpr (AXK == 1) {
-    if (d.axk == 1) rows_loss<TMW>(batch.rows, m0, p == 0 && n0 == 0, s_l);
-  }
-  if constexpr (AXA) {
+  // ---- the row block's loss partial, and the dL/da tail
+  if constexpr (ROWS == kRowsTile64) rows_loss<TMW>(batch.rows, m0, rows_writer, s_l);
+  if constexpr (SPREAD) {
     // the loss terms were staged by one thread per row: the writer workgroups (one per row
     // block) take a barrier of their own at the tail, where nothing else waits (a level
     // with dL/da partials shares the barrier below)
@@ -1438,7 +1424,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
       const float* s_t = s_pa;
       const float* s_w = s_pa + TMW * (TN + 1);
       __syncthreads();
-      if constexpr (AXA) rows_loss<TMW>(batch.rows, m0, rows_writer, s_l);
+      rows_loss<TMW>(batch.rows, m0, rows_writer, s_l);
       const int A = d.pa_A;
       constexpr int NSB = TN / 32;
       for (int e = tid; e < TMW * NSB * A; e += NTH) {
@@ -1457,12 +1443,12 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   SACMI_PHASE(batch.tl, 5);
 }
 
-template <int TM, int TN, int KSPLIT, int G, int MG, bool ADAM, int AXK = 0, bool BF16 = false>
+template <int TM, int TN, int KSPLIT, int G, int MG, bool ADAM, int ROWS = kRowsNone, bool BF16 = false>
 __global__ __launch_bounds__((gemm_threads<KSPLIT, MG>()), 4) void k_gemm(GemmBatch batch) {
   // (4 waves per SIMD: 16 waves per CU, one 1024- or two 512-thread workgroups)
   const TlMark tl_mark(batch.tl, TL_GEMM);
-  __shared__ KgSmem<TM, TN, KSPLIT, MG, AXK> sm;
-  kg_body<TM, TN, KSPLIT, G, MG, ADAM, AXK, BF16>(batch, blockIdx.x, sm);
+  __shared__ KgSmem<TM, TN, KSPLIT, MG, ROWS> sm;
+  kg_body<TM, TN, KSPLIT, G, MG, ADAM, ROWS, BF16>(batch, blockIdx.x, sm);
 }
 
 // Tile order and XCD placement.  Workgroups are dealt round-robin over the 8 XCDs
@@ -2668,7 +2654,7 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk16(GemmBatch batch) {
   gload(0);
   // the row prologue's loads and the ReLU-mask source, behind the first slab's loads
   RowsRegs rows_x{};
-  if constexpr (AX) rows_load<kXBM, NTH>(batch.rows, d, m0, rows_x);
+  if constexpr (AX) rows_load<kXBM, NTH>(batch.rows, m0, rows_x);
   float hm[2][NJ][4];
   dh_mask_load<ACT16>(d, hm, m0 + wm, n0 + wn, lane);
   swrite(0, 0, store_a);
@@ -2698,7 +2684,7 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk16(GemmBatch batch) {
     __syncthreads();
   }
   const bool writer = p == 0 && n0 == 0;
-  if constexpr (AX) rows_finish<kXBM, NTH>(batch.rows, d, m0, writer, bid == 0, rows_x, s_q, s_coef, s_l);
+  if constexpr (AX) rows_finish<kXBM, NTH>(batch.rows, m0, writer, bid == 0, rows_x, s_q, s_coef, s_l);
   dh_epilogue<AX>(d, acc, hm, s_coef, m0, wm, n0 + wn, lane);
   if constexpr (AX) rows_loss<kXBM>(batch.rows, m0, writer, s_l);
 }
@@ -2791,7 +2777,7 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk_x6(GemmBatch batch) {
   gload(0);
   // the row prologue's loads and the ReLU-mask source, behind the first slab's loads
   RowsRegs rows_x{};
-  if constexpr (AX) rows_load<kXBM, NTH>(batch.rows, d, m0, rows_x);
+  if constexpr (AX) rows_load<kXBM, NTH>(batch.rows, m0, rows_x);
   float hm[2][NJ][4];
   dh_mask_load<false>(d, hm, m0 + wm, n0 + wn, lane);
   swrite(0, store_a);
@@ -2825,7 +2811,7 @@ __global__ __launch_bounds__(64 * kAxWaves, 2) void k_axk_x6(GemmBatch batch) {
     }
   }
   const bool writer = p == 0 && n0 == 0;
-  if constexpr (AX) rows_finish<kXBM, NTH>(batch.rows, d, m0, writer, bid == 0, rows_x, s_q, s_coef, s_l);
+  if constexpr (AX) rows_finish<kXBM, NTH>(batch.rows, m0, writer, bid == 0, rows_x, s_q, s_coef, s_l);
   dh_epilogue<AX>(d, acc, hm, s_coef, m0, wm, n0 + wn, lane);
   if constexpr (AX) rows_loss<kXBM>(batch.rows, m0, writer, s_l);
 }
@@ -3088,11 +3074,12 @@ static int fwd_big_ok(GemmBatch& b) {
 }
 
 // one k_gemm configuration, fp32 or bf16 MFMA operands
-template <int TM, int TN, int KSPLIT, int G, int MG, bool ADAM, int AXK>
-static void launch_k(const GemmBatch& b, int grid, hipStream_t s) {
+template <int TM, int TN, int KSPLIT, int G, int MG, bool ADAM, int ROWS>
+static void launch_k(GemmBatch& b, int grid, hipStream_t s) {
   const dim3 blk(64 * KSPLIT * MG);
-  if (b.bf16) hipLaunchKernelGGL((k_gemm<TM, TN, KSPLIT, G, MG, ADAM, AXK, true>), dim3(grid), blk, 0, s, b);
-  else hipLaunchKernelGGL((k_gemm<TM, TN, KSPLIT, G, MG, ADAM, AXK, false>), dim3(grid), blk, 0, s, b);
+  if (b.bf16) hipLaunchKernelGGL((k_gemm<TM, TN, KSPLIT, G, MG, ADAM, ROWS, true>), dim3(grid), blk, 0, s, b);
+  else hipLaunchKernelGGL((k_gemm<TM, TN, KSPLIT, G, MG, ADAM, ROWS, false>), dim3(grid), blk, 0, s, b);
+  HIP_LAUNCH_CHECK();
 }
 
 // every desc's B operand has a bf16 shadow
@@ -3231,33 +3218,51 @@ static void launch_fwd_x6(GemmBatch& b, int, hipStream_t s) {
   HIP_LAUNCH_CHECK();
 }
 
-// whether every desc of the level is a plain dh desc with the A transform (k_gemm AXK 2):
-// axk 1, ReLU-mask epilogue, no bias, no bias-gradient column, no dot partials
-static bool axk_level_static(const GemmBatch& b) {
-  if (b.rows.kind != 1 && b.rows.kind != 2) return false;
+// Whether the level is a row-prologue level: no desc has the A transform (false), or every
+// desc is a plain dh desc with it — axk 1, ReLU-mask epilogue, no bias, no bias-gradient
+// column, no dot partials, no A K-scale — behind a critic or actor prologue (true).  Anything
+// in between throws: k_gemm, k_axk16 and k_axk_x6 compile the transform per level.
+static bool rows_level(const GemmBatch& b) {
+  int n_axk = 0, n_plain = 0;
   for (int i = 0; i < b.count; ++i) {
     const GemmDesc& d = b.d[i];
-    if (d.axk != 1 || d.epi != EPI_MASK || d.bias || d.rs_col >= 0 || d.dotp || d.a_ksc) return false;
+    n_axk += d.axk != 0;
+    n_plain += d.axk == 1 && d.epi == EPI_MASK && !d.bias && d.rs_col < 0 && !d.dotp && !d.a_ksc;
   }
+  if (n_axk == 0) return false;
+  if (n_plain != b.count || (b.rows.kind != 1 && b.rows.kind != 2))
+    throw Error{SACMI_ESTATE, "A transform on a level that is not a row-prologue dh level"};
   return true;
 }
 
-void launch_gemm(const GemmBatch& b0, hipStream_t s) {
-  if (b0.count == 0) return;
-  // the batch-4096-class kernels, in this order: the first whose probe takes the level
-  // (form >= 0) runs it.  A probe writes its tile assignment into b: each starts from b0.
+// The kernel choice of one level, made once: launch_gemm executes it, and
+// gemm_level_pa_capable asks it ahead of the launch.
+struct GemmPlan {
+  // a batch-4096-class kernel (the first of kBigKernels whose probe returns a form >= 0:
+  // arg) or one k_gemm configuration (launch_k; arg: its grid)
+  void (*launch)(GemmBatch&, int arg, hipStream_t) = nullptr;
+  int arg = 0;
+  int rows = kRowsNone;   // k_gemm: the prologue form of the configuration
+  GemmBatch b;            // the level with the chosen kernel's tile assignment and store policy
+};
+
+static GemmPlan plan_gemm_level(const GemmBatch& b0) {
+  // the batch-4096-class kernels, in this order.  A probe writes its tile assignment into
+  // b: each starts from b0.
   static constexpr struct {
     int (*probe)(GemmBatch&);
     void (*launch)(GemmBatch&, int form, hipStream_t);
-  } kBig[] = {{dw_split_plan, launch_dw_split}, {axk16_ok, launch_axk16}, {fwd_big_ok, launch_fwd16},
-              {fwd_x6_ok, launch_fwd_x6}, {axk_x6_ok, launch_axk_x6}};
-  GemmBatch b;
-  for (const auto& k : kBig) {
+  } kBigKernels[] = {{dw_split_plan, launch_dw_split}, {axk16_ok, launch_axk16}, {fwd_big_ok, launch_fwd16},
+                     {fwd_x6_ok, launch_fwd_x6}, {axk_x6_ok, launch_axk_x6}};
+  GemmPlan pl;
+  GemmBatch& b = pl.b;
+  const bool rows = rows_level(b0);
+  for (const auto& k : kBigKernels) {
     b = b0;
-    const int form = k.probe(b);
-    if (form >= 0) {
-      k.launch(b, form, s);
-      return;
+    pl.arg = k.probe(b);
+    if (pl.arg >= 0) {
+      pl.launch = k.launch;
+      return pl;
     }
   }
   b = b0;
@@ -3280,8 +3285,6 @@ void launch_gemm(const GemmBatch& b0, hipStream_t s) {
   // plain stores (config 3: 762 -> 774 us with every level write-through)
   b.st_wt = (n_adam > 0 || outs <= (1 << 20)) ? 1 : 0;
   // (Level::add guarantees a level is all-Adam or all-plain)
-  int axk = 0;
-  for (int i = 0; i < b.count; ++i) axk = b.d[i].axk > axk ? b.d[i].axk : axk;
   // weight-gradient levels (both operands row-contiguous): the Adam-fused and the plain
   // (data-parallel) form of a level take the same tile geometry, so their bits agree
   bool dw = true;
@@ -3289,8 +3292,8 @@ void launch_gemm(const GemmBatch& b0, hipStream_t s) {
   const int t64 = assign_tiles<32, 64>(b);
   if (dw && t64 <= 256) {
     // one 32x64 tile per CU (policy level): 16 waves, K split 16 ways
-    if (n_adam) launch_k<32, 64, 16, 1, 1, true, 0>(b, b.total_tiles + extra, s);
-    else launch_k<32, 64, 16, 1, 1, false, 0>(b, b.total_tiles + extra, s);
+    pl.launch = n_adam ? launch_k<32, 64, 16, 1, 1, true, kRowsNone> : launch_k<32, 64, 16, 1, 1, false, kRowsNone>;
+    pl.arg = b.total_tiles + extra;
   } else if (dw || n_adam || t64 > 512) {
     // more 32x64 tiles than CUs (the twin critic weight gradients; every level at large
     // batch): 64x64 tiles as two 32-row wave groups, each with a K split — half the operand
@@ -3299,29 +3302,36 @@ void launch_gemm(const GemmBatch& b0, hipStream_t s) {
     // or as two 512-thread ones (4-way): then one workgroup's LDS reduction and epilogue
     // overlap the other's operand loads and MFMAs (the dh and forward levels; the
     // weight-gradient levels keep the 8-way split).  Rides attach to 1024 threads.
-    const int g = assign_tiles<64, 64>(b) + extra;
+    pl.arg = assign_tiles<64, 64>(b) + extra;
     for (int i = 0; i < b.count; ++i)   // the two-wave-group tiles compute no dL/da partials
       if (b.d[i].pa_out) throw Error{SACMI_ESTATE, "dL/da partials requested on a 64-row tile level"};
-    if (n_adam) launch_k<32, 64, 8, 1, 2, true, 0>(b, g, s);
-    else if (dw) launch_k<32, 64, 8, 1, 2, false, 0>(b, g, s);   // the plain (data-parallel) form
-    else if (axk == 1 && !extra) launch_k<32, 64, 4, 1, 2, false, 1>(b, g, s);
-    else if (axk == 1) launch_k<32, 64, 8, 1, 2, false, 1>(b, g, s);
-    else if (!extra) launch_k<32, 64, 4, 1, 2, false, 0>(b, g, s);
-    else launch_k<32, 64, 8, 1, 2, false, 0>(b, g, s);
-  } else if (axk == 1) {
-    // dh1 / dha1 with the fc3 backward folded in (A transform, coefficient in the epilogue);
-    // a level of nothing but such descs (every one the update builds) runs the instantiation
-    // that compiles that path alone
-    const int g = assign_tiles<32, 32>(b) + extra;
-    if (axk_level_static(b)) launch_k<32, 32, 16, 2, 1, false, 2>(b, g, s);
-    else launch_k<32, 32, 16, 2, 1, false, 1>(b, g, s);
+    if (rows && extra) throw Error{SACMI_ESTATE, "ride on a row-prologue level of 64-row tiles"};
+    pl.rows = rows ? kRowsTile64 : kRowsNone;   // (a row-prologue level is neither dW nor Adam)
+    if (n_adam) pl.launch = launch_k<32, 64, 8, 1, 2, true, kRowsNone>;
+    else if (dw) pl.launch = launch_k<32, 64, 8, 1, 2, false, kRowsNone>;   // the plain (data-parallel) form
+    else if (rows) pl.launch = launch_k<32, 64, 4, 1, 2, false, kRowsTile64>;
+    else if (!extra) pl.launch = launch_k<32, 64, 4, 1, 2, false, kRowsNone>;
+    else pl.launch = launch_k<32, 64, 8, 1, 2, false, kRowsNone>;
+  } else if (rows) {
+    // dh1 / dha1 with the fc3 backward folded in (A transform, coefficient in the epilogue)
+    pl.launch = launch_k<32, 32, 16, 2, 1, false, kRowsSpread>;
+    pl.rows = kRowsSpread;
+    pl.arg = assign_tiles<32, 32>(b) + extra;
   } else if (t64 >= 192) {
     // widest tile that still gives one workgroup to most CUs
-    launch_k<32, 64, 16, 2, 1, false, 0>(b, b.total_tiles + extra, s);
+    pl.launch = launch_k<32, 64, 16, 2, 1, false, kRowsNone>;
+    pl.arg = b.total_tiles + extra;
   } else {
-    launch_k<32, 32, 16, 2, 1, false, 0>(b, assign_tiles<32, 32>(b) + extra, s);
+    pl.launch = launch_k<32, 32, 16, 2, 1, false, kRowsNone>;
+    pl.arg = assign_tiles<32, 32>(b) + extra;
   }
-  HIP_LAUNCH_CHECK();
+  return pl;
+}
+
+void launch_gemm(const GemmBatch& b0, hipStream_t s) {
+  if (b0.count == 0) return;
+  GemmPlan pl = plan_gemm_level(b0);
+  pl.launch(pl.b, pl.arg, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -3730,29 +3740,11 @@ void launch_sample_bwd_tail(const float* pa, int n_pa, const SampleBwdArgs& a, h
   HIP_LAUNCH_CHECK();
 }
 
-bool gemm_level_on_axk16(const GemmBatch& b0) {
-  GemmBatch b = b0;
-  return axk16_ok(b) >= 0;
-}
-
-// launch_gemm's own kernel choice for an axk-1 level, asked ahead of its launch: true when
-// it runs on the one-wave-group k_gemm tiles (<32, 32, 16, 2, 1, false, 1 or 2>: MG == 1, AXK
-// >= 1), the only form that computes dL/da partials.  Mirrors launch_gemm's order: the split-K
-// and the bf16 forward kernels never take an axk level; k_axk16 (bf16, batch-4096 class);
-// then the 64-row-tile branch (more than 512 32x64 tiles, e.g. batch 1024 with hidden > 512)
-bool gemm_level_pa_capable(const GemmBatch& b0) {
-  if (gemm_level_on_axk16(b0)) return false;
-  GemmBatch b = b0;
-  bool dw = true;
-  int axk = 0, n_adam = 0;
-  for (int i = 0; i < b.count; ++i) {
-    dw = dw && !b.d[i].a_kc && !b.d[i].b_kc;
-    axk = b.d[i].axk > axk ? b.d[i].axk : axk;
-    n_adam += b.d[i].epi >= EPI_ADAM;
-  }
-  const int t64 = assign_tiles<32, 64>(b);
-  if (dw || n_adam || t64 > 512) return false;
-  return axk == 1;
+// launch_gemm's own kernel choice for a row-prologue level, asked ahead of its launch: true
+// when it runs on the one-wave-group k_gemm tiles (kRowsSpread), the only form that computes
+// dL/da partials
+bool gemm_level_pa_capable(const GemmBatch& b) {
+  return b.count > 0 && plan_gemm_level(b).rows == kRowsSpread;
 }
 
 // ---------------------------------------------------------------------------

@@ -1202,8 +1202,8 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
     l9.b.bf16 = c->bf16 ? 1 : 0;
     // (batch <= 1024: the standalone L10 runs on B / 16 workgroups, too few to stream dha1;
     // at batch 4096 it fills the chip and the fold measured slower: config 3 L9 55 -> 71 us)
-    // (and only where launch_gemm takes the one-wave-group tiles that form the partials:
-    // batch 1024 with hidden > 512 goes to the 64-row tiles and keeps L10)
+    // (and only where launch_gemm's plan for the level is the one-wave-group tiles that form
+    // the partials: batch 1024 with hidden > 512 goes to the 64-row tiles and keeps L10)
     const bool fold_dlda = nh == 2 && B <= 1024 && !std::getenv("SACMI_NO_DLDA_FOLD") &&
                            gemm_level_pa_capable(l9.b);
     if (fold_dlda) {

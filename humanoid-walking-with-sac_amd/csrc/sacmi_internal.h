@@ -448,7 +448,7 @@ struct GemmBatch {
   AdamFuse adam;       // used when any desc has epi >= EPI_ADAM
   int has_adam;
   RideAlong ride;      // extra workgroups after the tiles
-  RowsFuse rows;       // prologue for axk-1 descs
+  RowsFuse rows;       // the level's row prologue (kind 1 / 2: then every desc is an axk-1 dh desc)
   int bf16;            // 1: bf16 MFMA operands (fp32 loads rounded to bf16 in registers)
   float* ws;           // bf16 deep-K weight-gradient levels: split-K partial workspace
   int64_t ws_floats;   //   (capacity; launch_gemm falls back when a level needs more)
@@ -517,9 +517,7 @@ void launch_gemm_sample_bwd(const GemmDesc& d, const SampleBwdArgs& a, hipStream
 // the same sample backward + dhp2 tail from the dL/da partials of the dha1 level
 // (GemmDesc::pa_out): dL/da = sum over the n_pa column blocks, fixed order
 void launch_sample_bwd_tail(const float* pa, int n_pa, const SampleBwdArgs& a, hipStream_t s);
-// whether launch_gemm runs this level on k_axk16 (no dL/da partials there)
-bool gemm_level_on_axk16(const GemmBatch& b);
-// whether launch_gemm runs this axk-1 level on the tiles that compute dL/da partials
+// whether launch_gemm runs this row-prologue level on the tiles that compute dL/da partials
 bool gemm_level_pa_capable(const GemmBatch& b);
 
 

@@ -1,6 +1,7 @@
-"""The row-prologue dh levels (L5 critic dh1, L9 actor dh1) on the k_gemm form that compiles
-the A-transform path alone (k_gemm AXK 2: the dot partials spread two per thread and summed
-by lane shuffles, the row coefficients formed per epilogue thread behind one barrier).
+"""The row-prologue dh levels (L5 critic dh1, L9 actor dh1) on k_gemm, in both forms of the
+prologue: the spread form of the 32x32 one-wave-group tiles (the dot partials two per thread
+and summed by lane shuffles, the row coefficients formed per epilogue thread behind one
+barrier) and the rows_load / rows_finish form of the 64-row two-wave-group tiles.
 
 Shapes (tools/gen_dh_rows_bits.py CASES), the smallest that reach every branch of the prologue:
   S11-A3-H96-B40      3 partials per row, a row tile with 8 live rows, the tile-0 ax_out
@@ -9,10 +10,13 @@ Shapes (tools/gen_dh_rows_bits.py CASES), the smallest that reach every branch o
   S11-A3-H544-B40     17 partials per row: hidden 544 at batch 40 is 36 32x64 tiles, so the
                       level still lands on the 32x32 axk k_gemm tiles and the sum runs its
                       tail loop past kRowsPv
+  S11-A3-H512-B1056   the smallest batch at hidden 512 on the 64-row tiles: 528 32x64 tiles
+                      (> 512), 272 64x64 and 136 64x128 tiles (< 512: not k_axk_x6)
 
 Bit pin: tests/golden/dh_rows_bits.json was written by tools/gen_dh_rows_bits.py on the commit
-BEFORE the level moved to the new form; the prologue's sums keep their order, so every loss
-and every parameter must come out bit for bit.  A later change which means to move these
+BEFORE the level moved to the spread form (the B 1056 record: before the prologue became a
+property of the level); the prologue's sums keep their order, so every loss and every
+parameter must come out bit for bit.  A later change which means to move these
 bits regenerates the file with that tool and says why.
 """
 import importlib.util
@@ -40,13 +44,47 @@ def golden_bits(golden_dir):
 
 
 def test_cases_land_on_the_axk_k_gemm_tiles():
-    """Every case's dh1 levels run on k_gemm (not k_axk16 / k_axk_x6), on the one-wave-group
-    32x32 tiles: fewer than 512 32x64 tiles over the two critics, which is also what makes
-    the H 544 case reach the tail of the partial sum (17 partials > kRowsPv = 16)."""
-    for name, S, A, H, B, *_ in gen.CASES:
-        t64 = 2 * ((B + 31) // 32) * ((H + 63) // 64)
-        assert t64 <= 512, name
-    assert [(c[3] + 31) // 32 for c in gen.CASES] == [3, 16, 17]
+    """Every case's dh1 levels run on k_gemm (not k_axk16 / k_axk_x6).  The first three on the
+    one-wave-group 32x32 tiles: at most 512 32x64 tiles over the two critics, which is also
+    what makes the H 544 case reach the tail of the partial sum (17 partials > kRowsPv = 16).
+    The B 1056 case on the 64-row two-wave-group tiles: more than 512 32x64 tiles, and fewer
+    than 512 64x64 / 64x128 tiles (k_axk_x6 wants 512 of either)."""
+    def tiles(B, H, tm, tn):
+        return 2 * ((B + tm - 1) // tm) * ((H + tn - 1) // tn)
+    for name, S, A, H, B, *_ in gen.CASES[:3]:
+        assert tiles(B, H, 32, 64) <= 512, name
+    name, S, A, H, B, *_ = gen.CASES[3]
+    assert (tiles(B, H, 32, 64), tiles(B, H, 64, 64), tiles(B, H, 64, 128)) == (528, 272, 136), name
+    assert [(c[3] + 31) // 32 for c in gen.CASES] == [3, 16, 17, 16]
+
+
+# case -> gridDim.x of its dh1 levels: 2 descs x 6 32x32 tiles, each desc padded to 8
+# workgroups; 2 descs x 136 64x64 tiles
+DH1_GRIDS = {"S11-A3-H96-B40": 16, "S11-A3-H512-B1056": 272}
+
+
+@pytest.mark.parametrize("name", sorted(DH1_GRIDS))
+def test_dh1_levels_run_k_gemm(name):
+    """The launch timeline's kernel and grid of L5 / L9: k_gemm in the 32x32 form at batch 40,
+    in the 64-row form at batch 1056."""
+    from oracle.sac_step import NETS
+    from sacmi import Config, Context
+    case = next(c for c in gen.CASES if c[0] == name)
+    cfg, params, rows, _ = gen.case_inputs(case)
+    B = case[4]
+    ctx = Context(Config(cfg.state_dim, cfg.action_dim, cfg.hidden_dim, max_batch=B, capacity=len(rows[2])), 0)
+    try:
+        for n in NETS:
+            ctx.set_net(n, params[n])
+        ctx.push(*rows)
+        ks, _ = ctx.profile_timeline(B, 1)
+    finally:
+        ctx.close()
+    by_site = {}
+    for k in ks:
+        by_site.setdefault(k["site"], set()).add((k["kernel"], k["grid"]))
+    for site in ("gemm_L5_critic_dh1", "gemm_L9_act_dh1"):
+        assert by_site.get(site) == {("k_gemm", DH1_GRIDS[name])}, (name, site, by_site.get(site))
 
 
 @pytest.mark.parametrize("case", gen.CASES, ids=CASE_IDS)

@@ -29,10 +29,14 @@ for _p in (ROOT, os.path.join(ROOT, "humanoid-walking-with-sac_amd")):
 #  * S376-A17-H512-B64: 16 partials per row (every lane of a (row, slot) group holds two),
 #    L9's dL/da partials at Humanoid's action width
 #  * S11-A3-H544-B40: 17 partials per row, the tail of the column-order sum
+#  * S11-A3-H512-B1056: the smallest batch at hidden 512 whose dh1 levels take the 64-row
+#    two-wave-group k_gemm tiles (528 32x64 tiles over the two critics), i.e. the
+#    rows_load / rows_finish form of the prologue
 CASES = (
     ("S11-A3-H96-B40", 11, 3, 96, 40, 160, 0.5, 701),
     ("S376-A17-H512-B64", 376, 17, 512, 64, 200, 0.1, 702),
     ("S11-A3-H544-B40", 11, 3, 544, 40, 160, 0.5, 703),
+    ("S11-A3-H512-B1056", 11, 3, 512, 1056, 1200, 0.5, 704),
 )
 UPDATES = 6
 
