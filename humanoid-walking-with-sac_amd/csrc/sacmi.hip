@@ -2667,18 +2667,58 @@ int sacmi_read_activation(sacmi_ctx* c, int32_t pass, int32_t layer, int32_t bat
     REQUIRE(pass >= 0 && pass <= 3 && layer >= 0 && layer < c->nh, SACMI_EVALUE, "bad (pass, layer)");
     REQUIRE(batch >= 1 && batch <= c->Bm, SACMI_EVALUE, "bad batch");
     REQUIRE(numel == (int64_t)2 * batch * c->H, SACMI_EVALUE, "numel must be 2 * batch * hidden");
-    REQUIRE(!act16_on(c, batch), SACMI_ESTATE, "activations of this batch are stored as bf16");
     CHECK_HIP(hipStreamSynchronize(c->stream));
-    const size_t H4 = (size_t)c->H * 4;
+    // act16 updates: the same element offsets and pitches in u16 elements (E() of the update
+    // builder); the bf16 rows are widened on the host
+    const bool a16 = act16_on(c, batch);
+    const size_t es = a16 ? 2 : 4, Hb = (size_t)c->H * es;
+    std::vector<uint16_t> h16(a16 ? (size_t)numel : 0);
+    char* dst = a16 ? reinterpret_cast<char*>(h16.data()) : reinterpret_cast<char*>(out);
     if (pass == 3) {
-      CHECK_HIP(hipMemcpy2D(out, H4, c->hp[layer].p, (size_t)c->Hd * 4, H4, (size_t)2 * batch,
+      CHECK_HIP(hipMemcpy2D(dst, Hb, c->hp[layer].p, (size_t)c->Hd * es, Hb, (size_t)2 * batch,
                             hipMemcpyDeviceToHost));
-      return;
+    } else {
+      const DevBuf<float>& b = pass == 0 ? c->hq[layer] : pass == 1 ? c->hqt[layer] : c->hqa[layer];
+      for (int i = 0; i < 2; ++i)
+        CHECK_HIP(hipMemcpy2D(dst + (size_t)i * batch * Hb, Hb, reinterpret_cast<const char*>(b.p) + (size_t)i * c->Hd * es,
+                              (size_t)2 * c->Hd * es, Hb, (size_t)batch, hipMemcpyDeviceToHost));
     }
-    const DevBuf<float>& b = pass == 0 ? c->hq[layer] : pass == 1 ? c->hqt[layer] : c->hqa[layer];
-    for (int i = 0; i < 2; ++i)
-      CHECK_HIP(hipMemcpy2D(out + (size_t)i * batch * c->H, H4, b.p + (size_t)i * c->Hd, (size_t)2 * c->Hd * 4, H4,
-                            (size_t)batch, hipMemcpyDeviceToHost));
+    if (a16) {
+      for (int64_t i = 0; i < numel; ++i) {
+        const uint32_t bits = (uint32_t)h16[(size_t)i] << 16;
+        std::memcpy(out + i, &bits, 4);
+      }
+    }
+  });
+}
+
+int sacmi_read_backward(sacmi_ctx* c, int32_t which, int32_t layer, int32_t batch, float* out,
+                        int64_t numel) {
+  return guard([&] {
+    REQUIRE(c && out, SACMI_EVALUE, "null argument");
+    REQUIRE(which >= SACMI_BWD_DHC && which <= SACMI_BWD_DOTP, SACMI_EVALUE, "bad buffer id");
+    REQUIRE(batch >= 1 && batch <= c->Bm, SACMI_EVALUE, "bad batch");
+    const bool per_layer = which <= SACMI_BWD_DHP;
+    REQUIRE(per_layer ? (layer >= 0 && layer < c->nh) : layer == 0, SACMI_EVALUE, "bad layer");
+    const int64_t B = batch, H = c->H, A = c->A;
+    const float* src = nullptr;
+    int64_t rows = 1, cols = 0, pitch = 0;      // rows x cols floats, source pitch in floats
+    switch (which) {
+      case SACMI_BWD_DHC: src = c->dhc[layer].p; cols = B * 2 * H; break;
+      case SACMI_BWD_DHA: src = c->dha[layer].p; cols = B * 2 * H; break;
+      case SACMI_BWD_DHP: src = c->dhp[layer].p; cols = B * H; break;
+      case SACMI_BWD_DQ: src = c->dq.p; cols = 2 * B; break;
+      case SACMI_BWD_DQ4: src = c->dq4.p; cols = 2 * B * 4; break;
+      case SACMI_BWD_DHEAD: src = c->dhead.p; rows = B; cols = 2 * A; pitch = c->lddh; break;
+      default: src = c->dotp.p; cols = 6 * B * c->nparts; break;
+    }
+    REQUIRE(numel == rows * cols, SACMI_EVALUE, "numel does not match the buffer");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    if (rows == 1)
+      CHECK_HIP(hipMemcpy(out, src, (size_t)cols * 4, hipMemcpyDeviceToHost));
+    else
+      CHECK_HIP(hipMemcpy2D(out, (size_t)cols * 4, src, (size_t)pitch * 4, (size_t)cols * 4, (size_t)rows,
+                            hipMemcpyDeviceToHost));
   });
 }
 

@@ -37,6 +37,7 @@ SLOT_PARAM, SLOT_GRAD, SLOT_ADAM_M, SLOT_ADAM_V = range(4)
 (S_LOG_ALPHA, S_ALPHA, S_ALPHA_IS_TENSOR, S_STEP_POLICY, S_STEP_Q1, S_STEP_Q2, S_STEP_ALPHA,
  S_ADAM_M_LOG_ALPHA, S_ADAM_V_LOG_ALPHA, S_GRAD_LOG_ALPHA, S_PER_FRAME,
  S_NOISE_COUNTER, S_KEEP_GRADS, S_GRAPH_COUNT) = range(14)
+BWD_DHC, BWD_DHA, BWD_DHP, BWD_DQ, BWD_DQ4, BWD_DHEAD, BWD_DOTP = range(7)   # sacmi_backward_buf
 
 
 class SacmiConfig(ctypes.Structure):
@@ -87,6 +88,7 @@ _PROTOS = {
     "sacmi_step_ride_possible": [c_vp, ctypes.c_int32, c_i32p],
     "sacmi_step_act16": [c_vp, ctypes.c_int32, c_i32p],
     "sacmi_read_activation": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int64],
+    "sacmi_read_backward": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int64],
     "sacmi_read_batch": [c_vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), c_f32p, ctypes.c_int64],
     "sacmi_fetch_losses": [c_vp, c_f32p, ctypes.c_int32, c_i32p],
     "sacmi_step_phase": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_float],

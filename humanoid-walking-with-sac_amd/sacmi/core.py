@@ -306,6 +306,18 @@ class Context:
         L.call("sacmi_read_activation", self._h, int(pass_), int(layer), int(batch), L.fptr(out), out.size)
         return out.reshape((2 * batch, H) if pass_ == 3 else (2, batch, H))
 
+    def read_backward(self, which: str, batch: int, layer: int = 0) -> np.ndarray:
+        """An fp32 backward buffer of the last update (sacmi.h sacmi_read_backward): dhc / dha
+        [batch, 2, hidden] (q1, q2), dhp [batch, hidden], dq [2, batch], dq4 [2 * batch, 4],
+        dhead [batch, 2 * action_dim], dotp [6, batch, ceil(hidden / 32)]."""
+        H, A = self.cfg.hidden_dim, self.cfg.action_dim
+        shape = {"dhc": (batch, 2, H), "dha": (batch, 2, H), "dhp": (batch, H), "dq": (2, batch),
+                 "dq4": (2 * batch, 4), "dhead": (batch, 2 * A), "dotp": (6, batch, (H + 31) // 32)}[which]
+        out = np.zeros(int(np.prod(shape)), np.float32)
+        L.call("sacmi_read_backward", self._h, getattr(L, "BWD_" + which.upper()), int(layer), int(batch),
+               L.fptr(out), out.size)
+        return out.reshape(shape)
+
     def read_batch(self, batch: int):
         """(idx[batch] int64, eps[2 * batch, A] float32) of the last device-sampled update of
         `batch` rows in batch set 0 (sacmi.h sacmi_read_batch): eps rows [0, batch) noise of

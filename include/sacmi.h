@@ -243,10 +243,30 @@ int sacmi_step_act16(sacmi_ctx* ctx, int32_t batch, int32_t* out);
  *   2  the updated critics on (s, a~)   -> [2][batch][hidden]
  *   3  the policy on [s' ; s]           -> [2 * batch][hidden]
  * (numel = 2 * batch * hidden).  Their signs are the ReLU masks the update's backward used:
- * the parity tests recompute the fp64 gradient under the GPU's own masks.  SACMI_ESTATE for
- * bf16-stored activations (sacmi_step_act16). */
+ * the parity tests recompute the fp64 gradient under the GPU's own masks.  bf16-stored
+ * activations (sacmi_step_act16) come back widened to fp32 (bits << 16: the exact stored
+ * values), in the same layout. */
 int sacmi_read_activation(sacmi_ctx* ctx, int32_t pass, int32_t layer, int32_t batch, float* out,
                           int64_t numel);
+/* Test hook (read-only: synchronises the stream and copies, launches nothing): an fp32
+ * backward buffer as the last update of `batch` rows left it in HBM.  `layer` is the hidden
+ * layer (0-based) of the per-layer buffers, 0 for the others.
+ *   DHC   [batch][2 * hidden]  dL/dh of the critics on (s, a), q1 | q2 side by side; for the
+ *         last hidden layer the coefficient-free rows u = [h > 0] w_head the row-prologue
+ *         level (L5) stored for that layer's weight gradient (dh = u * dq)
+ *   DHA   the same of the updated critics on (s, a~) (the last hidden layer's is never written)
+ *   DHP   [batch][hidden]      dL/dh of the policy's actor rows
+ *   DQ    [2][batch]           dL/dq_i = 2 (q_i - q^) / batch
+ *   DQ4   [2 * batch][4]       the same, one value per 16-byte row (pads 0)
+ *   DHEAD [batch][2 * action_dim]  dL/d(mean | log_std)
+ *   DOTP  [6][batch][(hidden + 31) / 32]  the critic head dot partials per 32-column block
+ *         (block 0 carries the head bias): slots 0/1 q1/q2 on (s, a), 2/3 the targets, 4/5
+ *         the updated critics on (s, a~); a row's head value is their fp32 sum in block order
+ * Additive: the ABI version is unchanged. */
+enum sacmi_backward_buf { SACMI_BWD_DHC = 0, SACMI_BWD_DHA = 1, SACMI_BWD_DHP = 2, SACMI_BWD_DQ = 3,
+                          SACMI_BWD_DQ4 = 4, SACMI_BWD_DHEAD = 5, SACMI_BWD_DOTP = 6 };
+int sacmi_read_backward(sacmi_ctx* ctx, int32_t which, int32_t layer, int32_t batch, float* out,
+                        int64_t numel);
 /* Test hook: the minibatch of the last device-sampled update of `batch` rows that used batch
  * set 0 (every single update, and the first of a multi-update graph): its replay indices
  * (idx[batch]: deque positions, or ring slots for PER) and the policy noise it drew

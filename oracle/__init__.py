@@ -19,6 +19,10 @@ per        numpy restatement of ``PrioritizedReplayBuffer`` sample / push /
 x6_model   bit-faithful numpy model of the batch-4096 fp32 GEMM kernels' three-way bf16
            operand split and six-product dot (kernels.hip x6_split4 / x6_mfma), with
            the adversarial-mantissa input classes of the x6 tests.
+bf16_model numpy model of the bf16 batch-4096 GEMM levels (k_fwd16 / k_fwd16p, k_axk16,
+           k_dw_part16 + k_dw_fin): the staging rounding bit for bit, the exact bf16
+           products summed in float64, the levels' forms, and the split-K row sums in
+           the kernels' own order of fp32 adds.
 heads_model analytic numpy model of the policy sample head (clamp, tanh squash, log-prob)
            and its backward as the HIP head kernels state them, in float32 or float64:
            the yardstick of the head-edge tests (tests/test_heads_model.py ties it to

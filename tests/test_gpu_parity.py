@@ -752,7 +752,8 @@ def test_bf16_compute_vs_emulation(S, A, n_hidden, B):
     deviation from exact arithmetic is bf16's own (fc1 dW ~7 %: strong cancellation over the
     batch), the kernel's extra error is accumulation-order level.  A second update is held
     to the same bars on oracles re-anchored on the GPU's state after the first
-    (oracle_from_ctx: Adam past its first step, alpha = exp(log_alpha), sac_imp.py:135)."""
+    (oracle_from_ctx: Adam past its first step, alpha = exp(log_alpha), sac_imp.py:135).
+    Kernel error is separated from rounding flips in tests/test_gpu_bf16_levels.py (per level)."""
     cfg = SacConfig(S, A, 512, n_hidden=n_hidden)
     params = init_params(cfg, 71, bias_scale=0.02)
     rows = synthetic_rows(cfg, max(2000, B + 1000), 72, state_scale=0.1)
