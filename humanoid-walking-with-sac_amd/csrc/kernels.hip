@@ -384,7 +384,9 @@ __device__ __forceinline__ void place_tile(const GemmDesc& d, int t, int& tr, in
 //                epilogue thread, the dL/da partials (it needs TMW * 4 * 8 <= threads)
 // A row-prologue level has the one core: fc3 backward folded into dh1 / dha1 (A = h2
 // transformed, B = W2).  (Layout dispatch: wave-uniform, once per workgroup.)
-constexpr int kRowsNone = 0, kRowsTile64 = 1, kRowsSpread = 2;
+//   kRowsTile64W the same with the rows' importance-sampling weights (kWgtAlways)
+constexpr int kRowsNone = 0, kRowsTile64 = 1, kRowsSpread = 2, kRowsTile64W = 3;
+constexpr bool rows_tile64(int rows) { return rows == kRowsTile64 || rows == kRowsTile64W; }
 template <int TM, int TN, int KSPLIT, int G, int MG, int ROWS, bool BF16, class Pre>
 __device__ __forceinline__ void gemm_core(const GemmDesc& d, int m0, int n0, float* red,
                                           float* rsum, bool rowsum, Pre&& pre) {
@@ -613,13 +615,21 @@ __device__ __forceinline__ void polyak_ride(const PolyakArgs& a, int w, int nw) 
 // only in rows_finish(): vmcnt retires in order, so a value consumed before the operand
 // burst would hold the burst back, and one loaded after it would wait for all of it.
 constexpr int kRowsPv = 16;    // dot partials held per (row, slot) thread: H <= 512
+// The row's importance-sampling weight (RowsFuse::w, prioritized replay with feedback) in a
+// kernel's prologue: kWgtAuto takes it where the level has one, else exactly 1.0f, on one code
+// path (k_axk16, k_axk_x6 and the spread form have the register for it); kWgtNone / kWgtAlways
+// are k_gemm's 64-row form, which has none to spare (the one more live value spills three
+// more VGPRs) and so keeps the unweighted level on the instantiation it had (kRowsTile64) and
+// takes the weighted one on its own (kRowsTile64W).
+constexpr int kWgtAuto = 0, kWgtNone = 1, kWgtAlways = 2;
 struct RowsRegs {
   float pv[kRowsPv];          // thread (row, slot) < TMW*nslot: the row's dot partials
   float r, d, lp, alpha;      // thread row < TMW: the row's own inputs
+  float w;                    // ... and its importance-sampling weight (RowsFuse::w, else unused)
   float lpa;                  // actor block 0, wave past the row threads: logp_part[lane]
 };
 
-template <int TMW, int NTH>
+template <int TMW, int NTH, int WGT = kWgtAuto>
 __device__ __forceinline__ void rows_load(const RowsFuse& rf, int m0, RowsRegs& x) {
   const int t = threadIdx.x;
   const int nslot = rf.kind == 1 ? 4 : 2;
@@ -632,6 +642,7 @@ __device__ __forceinline__ void rows_load(const RowsFuse& rf, int m0, RowsRegs& 
   const rsrc_t rR = make_rsrc(rf.kind == 1 ? rf.r : rf.logp, big);
   const rsrc_t rD = make_rsrc(rf.kind == 1 ? rf.d : rf.logp, big);
   const rsrc_t rLpa = make_rsrc(rf.logp_part ? rf.logp_part : rf.logp, rf.logp_part ? big : 0u);
+  const rsrc_t rW = make_rsrc(rf.w ? rf.w : rf.logp, rf.w ? big : 0u);
   const rsrc_t rSc = make_rsrc(&rf.sc->alpha, 4u);
   {
     const int row = t / nslot, sl = t % nslot;
@@ -647,26 +658,32 @@ __device__ __forceinline__ void rows_load(const RowsFuse& rf, int m0, RowsRegs& 
   x.lp = buf_ld(rLp, ob);
   x.r = buf_ld(rR, ob);
   x.d = buf_ld(rD, ob);
+  if constexpr (WGT != kWgtNone) x.w = buf_ld(rW, ob);
   const int lane = t - TMW * nslot;
   x.lpa = buf_ld(rLpa, (uint32_t)(2 * (lane >= 0 && lane < rf.n_lp ? lane : 0) + 1) * 4u);
 }
 
 // The coefficients (c0, c1) and loss terms (l0, l1) of batch row b from its head sums
 // q[0..3]: the one text of this arithmetic (rows_finish and k_gemm's spread form call it),
-// so the losses and dq bits do not depend on the kernel.
-template <class Regs>   // RowsRegs or Rows2Regs: the row's alpha, lp, r, d
+// so the losses and dq bits do not depend on the kernel.  Prioritized replay with feedback
+// (RowsFuse::w): the critic terms carry the row's importance-sampling weight — c_i = 2 w (q_i -
+// q^) / B, loss term w (q_i - q^)^2 — and td = (|q1 - q^| + |q2 - q^|) / 2 is the row's new
+// priority.  Without it w is exactly 1.0f on the same path: x * 1.0f is x, bit for bit.
+template <int WGT = kWgtAuto, class Regs>   // RowsRegs or Rows2Regs: the row's alpha, lp, r, d, w
 __device__ __forceinline__ void rows_coef(const RowsFuse& rf, int b, const float* q, const Regs& x,
-                                          float& c0, float& c1, float& l0, float& l1) {
-  c0 = 0.f; c1 = 0.f; l0 = 0.f; l1 = 0.f;
+                                          float& c0, float& c1, float& l0, float& l1, float& td) {
+  c0 = 0.f; c1 = 0.f; l0 = 0.f; l1 = 0.f; td = 0.f;
   if (b < rf.B) {
     if (rf.kind == 1) {
+      const float w = WGT == kWgtNone ? 1.f : (WGT == kWgtAlways || rf.w) ? x.w : 1.f;
       const float vt = fminf(q[2], q[3]) - x.alpha * x.lp;
       const float qhat = x.r + ((1.f - x.d) * rf.gamma) * vt;
       const float e1 = q[0] - qhat, e2 = q[1] - qhat;
-      c0 = 2.f * e1 / (float)rf.B;
-      c1 = 2.f * e2 / (float)rf.B;
-      l0 = e1 * e1;
-      l1 = e2 * e2;
+      c0 = 2.f * e1 / (float)rf.B * w;
+      c1 = 2.f * e2 / (float)rf.B * w;
+      l0 = e1 * e1 * w;
+      l1 = e2 * e2 * w;
+      td = 0.5f * (fabsf(e1) + fabsf(e2));
     } else {
       const float q1 = q[0], q2 = q[1];
       l0 = x.alpha * x.lp - fminf(q1, q2);
@@ -712,7 +729,7 @@ __device__ __forceinline__ void rows_actor_block0(const RowsFuse& rf, int lane, 
   }
 }
 
-template <int TMW, int NTH>
+template <int TMW, int NTH, int WGT = kWgtAuto>
 __device__ void rows_finish(const RowsFuse& rf, int m0, bool writer,
                             bool first_block, const RowsRegs& x0,
                             float (*s_q)[4], float (*s_coef)[TMW], float (*s_l)[2]) {
@@ -725,6 +742,7 @@ __device__ void rows_finish(const RowsFuse& rf, int m0, bool writer,
 #pragma unroll
   for (int q = 0; q < kRowsPv; ++q) asm volatile("" : "+v"(x.pv[q]));
   asm volatile("" : "+v"(x.r), "+v"(x.d), "+v"(x.lp), "+v"(x.lpa), "+v"(x.alpha));
+  if constexpr (WGT != kWgtNone) asm volatile("" : "+v"(x.w));
   if (t < TMW * nslot) {
     // the row's partials summed in column order (block 0's carries the fc3 bias)
     const int row = t / nslot, sl = t % nslot;
@@ -744,9 +762,11 @@ __device__ void rows_finish(const RowsFuse& rf, int m0, bool writer,
   SACMI_STAMP(36);
   const int b = m0 + t;
   if (t < TMW) {
-    float c0, c1, l0, l1;
-    rows_coef(rf, b, s_q[t], x, c0, c1, l0, l1);
+    float c0, c1, l0, l1, td;
+    rows_coef<WGT>(rf, b, s_q[t], x, c0, c1, l0, l1, td);
     if (b < rf.B) {
+      if constexpr (WGT != kWgtNone)
+        if (writer && rf.td) rf.td[b] = td;
       if (writer && rf.dq) { rf.dq[b] = c0; rf.dq[rf.B + b] = c1; }
       if (writer && rf.dq4) { rf.dq4[(size_t)b * 4] = c0; rf.dq4[((size_t)rf.B + b) * 4] = c1; }
     }
@@ -788,6 +808,7 @@ __device__ __forceinline__ void rows_loss(const RowsFuse& rf, int m0, bool write
 struct Rows2Regs {
   float pv[2];                // lane j of an eight-lane (row, slot) group: partials j, j + 8
   float r, d, lp, alpha;      // the thread's epilogue row
+  float w;                    // ... and its importance-sampling weight (RowsFuse::w, else unused)
   float lpa;                  // actor block 0, the wave past the (row, slot) threads: logp_part[lane]
 };
 
@@ -814,6 +835,7 @@ __device__ __forceinline__ void rows2_load(const RowsFuse& rf, int m0, Rows2Regs
   x.lp = rf.logp[ob];
   x.r = (critic ? rf.r : rf.logp)[ob];
   x.d = (critic ? rf.d : rf.logp)[ob];
+  x.w = (rf.w ? rf.w : rf.logp)[ob];
   const int lane = t - TMW * nslot;
   x.lpa = (rf.logp_part ? rf.logp_part : rf.logp)[lane >= 0 && lane < rf.n_lp ? (uint32_t)(2 * lane + 1) : 0u];
 }
@@ -827,7 +849,7 @@ __device__ __forceinline__ void rows2_sum(const RowsFuse& rf, int m0, bool first
   const bool critic = rf.kind == 1;
   const int nslot = critic ? 4 : 2;
   // pin every prologue value to this point (see rows_finish)
-  asm volatile("" : "+v"(x.pv[0]), "+v"(x.pv[1]), "+v"(x.r), "+v"(x.d), "+v"(x.lp), "+v"(x.lpa), "+v"(x.alpha));
+  asm volatile("" : "+v"(x.pv[0]), "+v"(x.pv[1]), "+v"(x.r), "+v"(x.d), "+v"(x.lp), "+v"(x.lpa), "+v"(x.alpha), "+v"(x.w));
   {
     const int pr = t >> 3;
     const int row = critic ? pr >> 2 : pr >> 1, sl = critic ? pr & 3 : pr & 1;
@@ -1005,6 +1027,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   // AX: a row-prologue level (every desc a plain dh desc with the A transform); SPREAD: its
   // 32x32 one-wave-group form, which also forms the dL/da partials (PA)
   constexpr bool AX = ROWS != kRowsNone, SPREAD = ROWS == kRowsSpread, PA = SPREAD;
+  constexpr int WGT = ROWS == kRowsTile64W ? kWgtAlways : kWgtNone;   // (the 64-row form's)
   static_assert(!AX || !ADAM, "a row-prologue level has no fused Adam");
   static_assert(!SPREAD || MG == 1, "the spread prologue: one wave group");
   // ---- locating the work: the scalar pins, the ride-along workgroups, the desc, the tile.
@@ -1196,7 +1219,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
     // consumed after the MFMAs: anything in flight at the k-loop header is waited for by
     // the back-edge's conservative vmcnt on the first iteration.
     if constexpr (SPREAD) rows2_load<TMW, TN>(batch.rows, m0, rows2_x);
-    else if constexpr (AX) rows_load<TMW, NTH>(batch.rows, m0, rows_x);
+    else if constexpr (AX) rows_load<TMW, NTH, WGT>(batch.rows, m0, rows_x);
     if constexpr (PA) {   // zero-length range where the level has no partials
       const rsrc_t rPW = make_rsrc(has_pa ? d.pa_w : d.C,
                                    has_pa ? (uint32_t)(((size_t)(d.N - 1) * d.pa_ld + d.pa_A) * 4) : 0u);
@@ -1260,8 +1283,8 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
       }
     }
   }
-  if constexpr (ROWS == kRowsTile64)
-    rows_finish<TMW, NTH>(batch.rows, m0, p == 0 && n0 == 0, bid == 0, rows_x, s_q, s_coef, s_l);
+  if constexpr (rows_tile64(ROWS))
+    rows_finish<TMW, NTH, WGT>(batch.rows, m0, p == 0 && n0 == 0, bid == 0, rows_x, s_q, s_coef, s_l);
   if constexpr (SPREAD) rows2_sum<TMW>(batch.rows, m0, bid == 0, rows2_x, s_q);
   __syncthreads();
   // the spread form: this thread's row coefficients, from the head sums the barrier published; the
@@ -1272,11 +1295,12 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
     SACMI_STAMP(36);
     const RowsFuse& rf = batch.rows;
     const int row = tid / TN, b = m0 + row;
-    float c0, c1, l0, l1;
-    rows_coef(rf, b, s_q[row], rows2_x, c0, c1, l0, l1);
+    float c0, c1, l0, l1, td;
+    rows_coef(rf, b, s_q[row], rows2_x, c0, c1, l0, l1, td);
     ax_coef = d.ax_slot ? c1 : c0;
     if (rows_writer && tid % TN == 0) {
       if (b < rf.B) {
+        if (rf.td) rf.td[b] = td;
         if (rf.dq) { rf.dq[b] = c0; rf.dq[rf.B + b] = c1; }
         if (rf.dq4) { rf.dq4[(size_t)b * 4] = c0; rf.dq4[((size_t)rf.B + b) * 4] = c1; }
       }
@@ -1406,7 +1430,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   if (threadIdx.x < 64) SACMI_STAMP(33);
   SACMI_PHASE(batch.tl, 4);
   // ---- the row block's loss partial, and the dL/da tail
-  if constexpr (ROWS == kRowsTile64) rows_loss<TMW>(batch.rows, m0, rows_writer, s_l);
+  if constexpr (rows_tile64(ROWS)) rows_loss<TMW>(batch.rows, m0, rows_writer, s_l);
   if constexpr (SPREAD) {
     // the loss terms were staged by one thread per row: the writer workgroups (one per row
     // block) take a barrier of their own at the tail, where nothing else waits (a level
@@ -3306,9 +3330,11 @@ static GemmPlan plan_gemm_level(const GemmBatch& b0) {
     for (int i = 0; i < b.count; ++i)   // the two-wave-group tiles compute no dL/da partials
       if (b.d[i].pa_out) throw Error{SACMI_ESTATE, "dL/da partials requested on a 64-row tile level"};
     if (rows && extra) throw Error{SACMI_ESTATE, "ride on a row-prologue level of 64-row tiles"};
-    pl.rows = rows ? kRowsTile64 : kRowsNone;   // (a row-prologue level is neither dW nor Adam)
+    // (a row-prologue level is neither dW nor Adam)
+    pl.rows = rows ? (b.rows.w ? kRowsTile64W : kRowsTile64) : kRowsNone;
     if (n_adam) pl.launch = launch_k<32, 64, 8, 1, 2, true, kRowsNone>;
     else if (dw) pl.launch = launch_k<32, 64, 8, 1, 2, false, kRowsNone>;   // the plain (data-parallel) form
+    else if (rows && b.rows.w) pl.launch = launch_k<32, 64, 4, 1, 2, false, kRowsTile64W>;
     else if (rows) pl.launch = launch_k<32, 64, 4, 1, 2, false, kRowsTile64>;
     else if (!extra) pl.launch = launch_k<32, 64, 4, 1, 2, false, kRowsNone>;
     else pl.launch = launch_k<32, 64, 8, 1, 2, false, kRowsNone>;

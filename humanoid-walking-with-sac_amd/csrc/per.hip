@@ -767,4 +767,43 @@ void launch_per_update(float* prio, const int64_t* idx, const float* val, int64_
   launch_check("PER update_priorities");
 }
 
+// ---------------------------------------------------------------------------
+// Feedback (sacmi_per_set_feedback): update_priorities(idx, td) of the update's own minibatch,
+// from the TD errors its L5 row prologue left in a.td — priority = float32(float64(td) + 1e-6)
+// (replay_buffer.py:86: priority.item() + 1e-6), last duplicate wins.  The owner-claim scheme
+// of k_owner_* in ONE launch of ONE workgroup: a device-sampled batch is at most 4096 rows (four
+// per thread), so the three steps are separated by the workgroup's own barrier — the claims are
+// L2 atomics, the owner reads bypass the vector cache — and no workgroup waits on another.
+// An update the error bits void (any bit: the reference raised before update_priorities)
+// writes nothing.  A non-finite td is written as it is: the next draw then reports it.
+__global__ __launch_bounds__(1024) void k_per_feedback(PerFeedbackArgs a) {
+  const TlMark tl_mark(a.tl, TL_PER_FEEDBACK);
+  if (__atomic_load_n(a.err, __ATOMIC_RELAXED)) return;   // (uniform: before any barrier)
+  const int t = threadIdx.x;
+  for (int i = t; i < a.n; i += blockDim.x) {
+    const int64_t slot = a.idx[i];
+    if ((uint64_t)slot < (uint64_t)a.cap) atomicMax(&a.owner[slot], (int32_t)i);
+  }
+  __threadfence();
+  __syncthreads();
+  for (int i = t; i < a.n; i += blockDim.x) {
+    const int64_t slot = a.idx[i];
+    const float v = (float)((double)a.td[i] + 1e-6);
+    a.stored[i] = v;
+    if ((uint64_t)slot < (uint64_t)a.cap &&
+        __hip_atomic_load(&a.owner[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int32_t)i)
+      a.prio[slot] = v;
+  }
+  __syncthreads();
+  for (int i = t; i < a.n; i += blockDim.x) {
+    const int64_t slot = a.idx[i];
+    if ((uint64_t)slot < (uint64_t)a.cap) a.owner[slot] = -1;
+  }
+}
+
+void launch_per_feedback(const PerFeedbackArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_per_feedback, dim3(1), dim3(1024), 0, s, a);
+  launch_check("PER feedback");
+}
+
 }  // namespace sacmi

@@ -263,6 +263,12 @@ struct sacmi_ctx {
   float* ring_host = nullptr;               // [ring_slots][3] loss readback staging
   // PER scratch (replay_kind == PER)
   sacmi::DevBuf<float> per_probs, per_chunk, per_w, per_val;
+  // per batch set (BatchBufs; b: set 1): the draw's importance-sampling weights, and in
+  // feedback mode the update's TD errors (L5) and the priorities written back from them
+  sacmi::DevBuf<float> per_wb, per_td, per_tdb, per_pv, per_pvb;
+  // sacmi_per_set_feedback: device-sampled updates weight the critic loss with the draw's
+  // weights and write |TD| back as the sampled rows' priorities
+  bool per_feedback = false;
   sacmi::DevBuf<int64_t> per_q, per_blk, per_idx;
   sacmi::DevBuf<double> per_cdf, per_u, per_uin;
   sacmi::DevBuf<int32_t> per_owner, per_bad;
@@ -450,6 +456,9 @@ static void alloc_all(sacmi_ctx* c) {
     c->per_u.alloc(c->Bm + 2);
     c->per_uin.alloc(c->Bm + 2);
     c->per_w.alloc(c->Bm + 2);
+    c->per_wb.alloc(c->Bm + 2);
+    c->per_td.alloc(c->Bm); c->per_tdb.alloc(c->Bm);
+    c->per_pv.alloc(c->Bm); c->per_pvb.alloc(c->Bm);
   }
   c->mt.alloc(2 * 625);
   c->mt_pf.alloc(625);
@@ -773,7 +782,8 @@ static bool mark(sacmi_ctx* c, const char* name, double flops = 0, double bytes 
 
 struct BatchBufs;
 static PerArgs per_args(sacmi_ctx* c, int k, int gen_u, const BatchBufs* bb = nullptr);
-static PerArgs per_args_impl(sacmi_ctx* c, int k, int gen_u, int32_t* idx32, int64_t* idx64) {
+static PerArgs per_args_impl(sacmi_ctx* c, int k, int gen_u, int32_t* idx32, int64_t* idx64,
+                             float* w) {
   PerArgs a{};
   a.prio = c->prio.p; a.len = c->len; a.cap = c->capacity; a.alpha = (float)c->cfg.per_alpha;
   a.probs = c->per_probs.p; a.chunk_sums = c->per_chunk.p; a.q = c->per_q.p;
@@ -781,26 +791,32 @@ static PerArgs per_args_impl(sacmi_ctx* c, int k, int gen_u, int32_t* idx32, int
   a.mt = c->mt.p + 625; a.gen_u = gen_u; a.u = c->per_uin.p; a.u_scratch = c->per_u.p;
   a.k = k; a.sc = c->sc.p; a.beta_start = c->cfg.per_beta_start;
   a.beta_frames = c->cfg.per_beta_frames; a.idx32 = idx32; a.idx_out = idx64;
-  a.w_out = c->per_w.p;
+  a.w_out = w;
   a.err = &c->sc.p->err; a.mt_backup = c->mt_backup.p;
   a.skip_on_err = 1;       // update graphs; the host API (sacmi_per_sample) clears it
   return a;
 }
 
-// The minibatch buffers of one update (indices, gathered rows, r, d): set 0 is the one
+// The minibatch buffers of one update (indices, gathered rows, r, d; prioritized replay: the
+// draw's weights, the update's TD errors and written-back priorities): set 0 is the one
 // every single update and the host-side APIs use; set 1 serves the odd updates of a
-// multi-update graph, so that the next update's gather can run while this one still
-// reads its rows.
+// multi-update graph, so that the next update's sampler and gather can run while this one
+// still reads its rows (and, in feedback mode, its weights).
 struct BatchBufs {
   int32_t* idx32; int64_t* idx64; float* xq; float* x2; float* r; float* d;
+  float* w; float* td; float* pv;   // (null on a uniform context)
 };
 static BatchBufs batch_bufs(sacmi_ctx* c, int parity) {
-  if (parity == 0) return BatchBufs{c->idx32.p, c->idx64.p, c->xq.p, c->x2.p, c->r.p, c->d.p};
-  return BatchBufs{c->idx32b.p, c->idx64b.p, c->xqb.p, c->x2b.p, c->rb.p, c->db.p};
+  if (parity == 0)
+    return BatchBufs{c->idx32.p, c->idx64.p, c->xq.p, c->x2.p, c->r.p, c->d.p,
+                     c->per_w.p, c->per_td.p, c->per_pv.p};
+  return BatchBufs{c->idx32b.p, c->idx64b.p, c->xqb.p, c->x2b.p, c->rb.p, c->db.p,
+                   c->per_wb.p, c->per_tdb.p, c->per_pvb.p};
 }
 // the prioritized sampler writes the indices of batch set bb (set 0 by default)
 static PerArgs per_args(sacmi_ctx* c, int k, int gen_u, const BatchBufs* bb) {
-  return per_args_impl(c, k, gen_u, bb ? bb->idx32 : c->idx32.p, bb ? bb->idx64 : c->idx64.p);
+  return per_args_impl(c, k, gen_u, bb ? bb->idx32 : c->idx32.p, bb ? bb->idx64 : c->idx64.p,
+                       bb ? bb->w : c->per_w.p);
 }
 
 static int sample_setsize(int k) {   // random.py:486-488
@@ -948,13 +964,49 @@ static void require_moments_readable(const sacmi_ctx* c) {
   require_moments_whole(c);
 }
 
+// Feedback mode (sacmi_per_set_feedback): a device-sampled update of a prioritized context is
+// the closed loop — its critic row prologue (L5) takes the draw's importance-sampling weights
+// and leaves the rows' TD errors, and k_per_feedback writes them back as priorities.
+static bool feedback_on(const sacmi_ctx* c, int dev_idx) {
+  return c->per_feedback && dev_idx && c->cfg.replay_kind == SACMI_REPLAY_PER;
+}
+
+// update_priorities(idx, td) of the update on batch set bb, on stream s
+static void enqueue_feedback(sacmi_ctx* c, int B, const BatchBufs& bb, hipStream_t s) {
+  if (!mark(c, "per_feedback")) return;
+  PerFeedbackArgs f{};
+  f.prio = c->prio.p; f.cap = c->capacity; f.idx = bb.idx64; f.td = bb.td; f.n = B;
+  f.owner = c->per_owner.p; f.stored = bb.pv; f.err = &c->sc.p->err; f.tl = c->tl_cur;
+  check_span(f.idx, B - 1, "feedback idx");
+  check_span(f.td, B - 1, "feedback td");
+  check_span(f.stored, B - 1, "feedback stored");
+  check_span(f.owner, c->capacity - 1, "feedback owner");
+  check_span(f.prio, c->capacity - 1, "feedback prio");
+  launch_per_feedback(f, s);
+}
+
+// Feedback mode, update r of a multi-update graph that has a successor, called once r's L5 is
+// enqueued: the side stream forks here, writes update r's priorities back, then draws and
+// gathers update r + 1's batch (into the other set); update r + 1 joins on side_ev[2r + 3].
+static void fork_feedback(sacmi_ctx* c, int B, int r) {
+  CHECK_HIP(hipEventRecord(c->side_ev[2 * r], c->stream));
+  CHECK_HIP(hipStreamWaitEvent(c->side_stream, c->side_ev[2 * r], 0));
+  enqueue_feedback(c, B, batch_bufs(c, r & 1), c->side_stream);
+  enqueue_sample_gather(c, B, (r + 1) & 1, true, c->side_stream, "_next");
+  CHECK_HIP(hipEventRecord(c->side_ev[2 * r + 3], c->side_stream));
+}
+
 // parity: which batch buffer set this update uses; have_batch: its indices and rows
 // were produced by the previous update's ride-along work; ride_next: produce the next
 // update's (into the other set) inside this update's L11 / L13 launches.
+// fork_r (feedback mode): >= 0 for update fork_r of a multi-update graph that has a successor —
+// fork_feedback runs behind its L5; -1: the write-back is this update's last launch.
 static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_mask,
                            float grad_scale, bool use_ring, int parity = 0,
-                           bool have_batch = false, bool ride_next = false) {
+                           bool have_batch = false, bool ride_next = false, int fork_r = -1) {
   hipStream_t s = c->stream;
+  const bool fb = feedback_on(c, dev_idx);
+  REQUIRE(!fb || phase_mask == 7, SACMI_ESTATE, "prioritized feedback needs the fused update");
   // every Adam step of this update but the sharded data-parallel form's own (enqueue_dp_sharded
   // steps this rank's chunks) reads and writes the whole of M, V
   if ((phase_mask & 6) && !c->dp_sharding_now) require_moments_whole(c);
@@ -1049,6 +1101,11 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
       rf.r = bb.r; rf.d = bb.d; rf.logp = c->logp.p; rf.logp_a = c->logp.p + B;
       rf.gamma = (float)c->cfg.gamma;
       rf.sc = c->sc.p; rf.dq = c->dq.p; rf.dq4 = c->dq4.p; rf.loss_part = c->lpart_c.p;
+      if (fb) {
+        rf.w = bb.w; rf.td = bb.td;
+        check_span(rf.w, B - 1, "rows w");
+        check_span(rf.td, B - 1, "rows td");
+      }
     }
     // L1: policy fc1 on [s2 ; s] (2B rows), critic fc1 (twin) on [s|1|a]
     Level l1;
@@ -1090,6 +1147,7 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
       run(lv, l == 1 ? "gemm_L4_tgt_fc2" : "gemm_L4b_tgt_fc3");
     }
     run(l5, "gemm_L5_critic_dh1");
+    if (fb && fork_r >= 0) fork_feedback(c, B, fork_r);
     // L5b (3 hidden layers): dh[l-1] = (dh[l] W[l]) * relu'(h[l-1]) down to dh[0]
     for (int l = L - 1; l >= 1; --l) {
       Level lv;
@@ -1312,6 +1370,8 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
       run(l12, "gemm_L12_pi_dhp1");
     }
     run(l13, fuse ? "gemm_L13_pi_dW_adam" : "gemm_L13_pi_dW1");
+    // (off the chain in front of L6: nothing of this update reads the priorities)
+    if (fb && fork_r < 0) enqueue_feedback(c, B, bb, s);
   }
   if ((phase_mask & 4) && phase_mask != 7) {
     AdamArgs ad = dp_adam_args(c, false, B, grad_scale, use_ring);
@@ -1368,8 +1428,18 @@ static void enqueue_many(sacmi_ctx* c, int B, int dev_idx, int dev_eps, bool use
     // stream's gather (join).  The side stream's own order keeps the sampling stream's
     // state (MT / numpy MT + frame) sequential, exactly as n separate updates consume it.
     enqueue_sample_gather(c, B, 0, true, c->stream);
+    // feedback mode: update r + 1's draw reads the priorities update r writes back, and
+    // those exist once its L5 has run — the fork moves from update r's start to behind its
+    // L5; the side stream takes the write-back, then the draw and the gather, beside L6-L13.
+    // (The last update has nothing to fork for: its write-back is its own last launch.)
+    const bool fb = feedback_on(c, dev_idx);
     for (int r = 0; r < reps; ++r) {
       if (r > 0) CHECK_HIP(hipStreamWaitEvent(c->stream, c->side_ev[2 * r + 1], 0));
+      if (fb) {
+        enqueue_update(c, B, dev_idx, dev_eps, 7, 1.f, use_ring, r & 1, true, false,
+                       r + 1 < reps ? r : -1);
+        continue;
+      }
       if (r + 1 < reps) {
         CHECK_HIP(hipEventRecord(c->side_ev[2 * r], c->stream));
         CHECK_HIP(hipStreamWaitEvent(c->side_stream, c->side_ev[2 * r], 0));
@@ -1394,6 +1464,9 @@ static void enqueue_many(sacmi_ctx* c, int B, int dev_idx, int dev_eps, bool use
 
 static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_mask,
                        float grad_scale, bool use_ring, int reps = 1, PhaseRide pr = {}) {
+  REQUIRE(!c->per_feedback || (dev_idx && phase_mask == 7), SACMI_ESTATE,
+          "prioritized feedback is on: the update samples on the device (no staged indices, "
+          "no phase-split or data-parallel update)");
   if (phase_mask & 6) require_moments_whole(c);   // (before any state changes; enqueue_update)
   c->pf_save = false;
   if (!c->mb_graph) mb_flush(c);   // (mb_graph: this update's sampler takes them)
@@ -1431,12 +1504,20 @@ static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_
   GraphKey key{B, dev_idx, dev_eps,
                phase_mask | (grad_scale != 1.f ? 8 : 0) | (c->keep_grads ? 16 : 0) |
                    (pr.parity ? 32 : 0) | (pr.have_batch ? 64 : 0) | (pr.ride_next ? 128 : 0) |
-                   (c->mb_graph ? 256 : 0),
+                   (c->mb_graph ? 256 : 0) | (c->per_feedback ? 512 : 0),
                use_ring ? c->ring_slots : 0,
                per_graph_len(c), reps};
   auto it = c->graphs.find(key);
   if (it == c->graphs.end()) it = c->graphs.emplace(key, capture_graph(c, enqueue_all)).first;
   CHECK_HIP(hipGraphLaunch(it->second, c->stream));
+}
+
+// the phase-split and data-parallel updates of a context in feedback mode: each rank would
+// write its own minibatch's priorities into its own replica of the array (sharded
+// priorities are not built)
+static void refuse_feedback(const sacmi_ctx* c) {
+  REQUIRE(!(c && c->per_feedback), SACMI_ESTATE,
+          "prioritized feedback is on: no phase-split or data-parallel update");
 }
 
 static void check_batch(sacmi_ctx* c, int B) {
@@ -1882,7 +1963,8 @@ int sacmi_destroy(sacmi_ctx* c) {
                     &c->db, &c->eps,
                     &c->cache, &c->logp, &c->dq, &c->dq4, &c->dotp, &c->pa, &c->act_h, &c->dw_ws, &c->dhead, &c->lpart_c, &c->lpart_a, &c->ring, &c->lp_part, &c->dp_flags, &c->ax, &c->ah1, &c->ah2,
                     &c->aeps, &c->acache, &c->alogp, &c->aout, &c->stage, &c->per_scr, &c->per_probs,
-                    &c->per_chunk, &c->per_w, &c->per_val})
+                    &c->per_chunk, &c->per_w, &c->per_val, &c->per_wb, &c->per_td, &c->per_tdb,
+                    &c->per_pv, &c->per_pvb})
       b->release();
     for (int l = 0; l < 3; ++l)
       for (auto* b : {&c->hp[l], &c->hq[l], &c->hqt[l], &c->hqa[l], &c->dhc[l], &c->dha[l], &c->dhp[l]})
@@ -2442,6 +2524,9 @@ static void step_finish(sacmi_ctx* c, int batch, float* losses_out, int done_pre
 int sacmi_step(sacmi_ctx* c, int32_t batch, const int64_t* idx, const float* eps1,
                const float* eps2, float* losses_out) {
   return guard([&] {
+    // (before anything is staged: a refused call leaves no trace)
+    REQUIRE(!(c && c->per_feedback && idx), SACMI_ESTATE,
+            "prioritized feedback is on: the update samples on the device (no staged indices)");
     check_batch(c, batch);
     REQUIRE(idx || batch <= 4096, SACMI_EVALUE, "device random.sample supports batch <= 4096");
     stage_inputs(c, batch, idx, eps1, eps2);
@@ -2520,6 +2605,7 @@ int sacmi_fetch_losses(sacmi_ctx* c, float* out, int32_t max_steps, int32_t* n_o
 int sacmi_step_phase(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_scale) {
   return guard([&] {
     pf_touch(c);
+    refuse_feedback(c);
     REQUIRE(phase >= 0 && phase <= 3, SACMI_EVALUE, "phase must be 0, 1, 2 or 3");
     if (phase == 0 || phase == 3) check_device_batch(c, batch);
     run_update(c, batch, 1, 1, phase == 3 ? 5 : 1 << phase, grad_scale, false);
@@ -2530,6 +2616,7 @@ int sacmi_step_phase_ex(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_s
                         int32_t parity, int32_t have_batch, int32_t ride_next) {
   return guard([&] {
     pf_touch(c);
+    refuse_feedback(c);
     REQUIRE(phase >= 0 && phase <= 3, SACMI_EVALUE, "phase must be 0, 1, 2 or 3");
     REQUIRE(parity == 0 || parity == 1, SACMI_EVALUE, "parity must be 0 or 1");
     if (phase == 0 || phase == 3) check_device_batch(c, batch);
@@ -2589,6 +2676,7 @@ int sacmi_dp_loopback_init(sacmi_ctx* c, int32_t world) {
 int sacmi_step_dp(sacmi_ctx* c, int32_t batch, int32_t n_updates) {
   return guard([&] {
     pf_touch(c);
+    refuse_feedback(c);
     mb_flush(c);
     REQUIRE(c->comm || c->dp_loopback, SACMI_ESTATE, "sacmi_allreduce_init has not been called");
     check_device_batch(c, batch);
@@ -2975,6 +3063,7 @@ int sacmi_profile_timeline_dp(sacmi_ctx* c, int32_t batch, int32_t n_updates, in
                               int32_t* n_kernels, double* graph_us) {
   return guard([&] {
     pf_touch(c);
+    refuse_feedback(c);
     mb_flush(c);
     REQUIRE(c->comm || c->dp_loopback, SACMI_ESTATE, "sacmi_allreduce_init has not been called");
     check_device_batch(c, batch);
@@ -3045,6 +3134,36 @@ int sacmi_per_get_priorities(sacmi_ctx* c, float* out, int64_t n) {
     REQUIRE(n >= 0 && n <= c->capacity, SACMI_EVALUE, "n > capacity");
     CHECK_HIP(hipStreamSynchronize(c->stream));
     CHECK_HIP(hipMemcpy(out, c->prio.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int sacmi_per_set_feedback(sacmi_ctx* c, int32_t on) {
+  return guard([&] {
+    REQUIRE(c, SACMI_EVALUE, "null ctx");
+    pf_touch(c);
+    require_per(c);
+    c->per_feedback = on != 0;     // (part of the graph key: both forms stay captured)
+  });
+}
+
+int sacmi_per_feedback(sacmi_ctx* c, int32_t* on) {
+  return guard([&] {
+    REQUIRE(c && on, SACMI_EVALUE, "null argument");
+    require_per(c);
+    *on = c->per_feedback ? 1 : 0;
+  });
+}
+
+int sacmi_read_per_feedback(sacmi_ctx* c, int32_t batch, float* weights, float* td, float* stored) {
+  return guard([&] {
+    REQUIRE(c, SACMI_EVALUE, "null ctx");
+    require_per(c);
+    REQUIRE(batch >= 1 && batch <= c->Bm, SACMI_EVALUE, "bad batch");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    const size_t nb = (size_t)batch * 4;
+    if (weights) CHECK_HIP(hipMemcpy(weights, c->per_w.p, nb, hipMemcpyDeviceToHost));
+    if (td) CHECK_HIP(hipMemcpy(td, c->per_td.p, nb, hipMemcpyDeviceToHost));
+    if (stored) CHECK_HIP(hipMemcpy(stored, c->per_pv.p, nb, hipMemcpyDeviceToHost));
   });
 }
 

@@ -110,7 +110,8 @@ typedef unsigned long long tl_word;
 enum TlKind : int {
   TL_GEMM = 1, TL_FWD_X6, TL_FWD16, TL_AXK16, TL_AXK_X6, TL_DW_PART16, TL_DW_FIN, TL_HEADS,
   TL_SAMPLE_BWD, TL_MT_SAMPLE, TL_GATHER, TL_PER_F1, TL_PER_F2, TL_PER_F2B, TL_PER_F3,
-  TL_PER_F4, TL_PER_UNFUSED, TL_ADAM, TL_SAMPLE_TAIL, TL_FWD16P, TL_DW_PART_X6, TL_KINDS
+  TL_PER_F4, TL_PER_UNFUSED, TL_ADAM, TL_SAMPLE_TAIL, TL_FWD16P, TL_DW_PART_X6,
+  TL_PER_FEEDBACK, TL_KINDS
 };
 constexpr int kTlEnd = 4;            // first of the ~end slots
 constexpr int kTlEndSlots = 4096;
@@ -405,6 +406,11 @@ struct RowsFuse {
   float* alpha_grad;
   const float* logp_part;
   int n_lp;
+  // critic, prioritized replay with feedback (else null): the rows' importance-sampling
+  // weights [B] (the sampler's w_out) and, out, the rows' TD errors (|q1 - q^| + |q2 - q^|) / 2
+  // [B], the priorities k_per_feedback writes back
+  const float* w;
+  float* td;
 };
 
 constexpr int kMaxGemms = 8;
@@ -637,5 +643,17 @@ void launch_per_update(float* prio, const int64_t* idx, const float* val, int64_
                        int32_t* owner, hipStream_t s);
 void launch_per_push(float* prio, int64_t cap, int64_t pos, int64_t n, int empty, float* scratch,
                      hipStream_t s);
+// The update's own update_priorities (feedback mode; k_per_feedback): one workgroup
+struct PerFeedbackArgs {
+  float* prio; int64_t cap;
+  const int64_t* idx;     // [n] the update's ring slots (the sampler's idx_out)
+  const float* td;        // [n] its rows' TD errors (RowsFuse::td)
+  int n;
+  int32_t* owner;         // [cap], -1 everywhere between launches
+  float* stored;          // [n] out: float32(float64(td) + 1e-6), the values written
+  const int* err;         // ErrBits: any bit set -> nothing is written
+  tl_word* tl;
+};
+void launch_per_feedback(const PerFeedbackArgs& a, hipStream_t s);
 
 }  // namespace sacmi

@@ -99,6 +99,9 @@ _PROTOS = {
     "sacmi_per_update": [c_vp, c_i64p, c_f32p, ctypes.c_int64],
     "sacmi_per_get_priorities": [c_vp, c_f32p, ctypes.c_int64],
     "sacmi_per_set_priorities": [c_vp, c_f32p, ctypes.c_int64],
+    "sacmi_per_set_feedback": [c_vp, ctypes.c_int32],
+    "sacmi_per_feedback": [c_vp, c_i32p],
+    "sacmi_read_per_feedback": [c_vp, ctypes.c_int32, c_f32p, c_f32p, c_f32p],
     "sacmi_act": [c_vp, c_f32p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p],
     "sacmi_allreduce_unique_id": [ctypes.c_char_p, ctypes.c_int32],
     "sacmi_allreduce_init": [c_vp, ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32],
@@ -124,7 +127,7 @@ TL_KINDS = {1: "k_gemm", 2: "k_fwd_x6", 3: "k_fwd16", 4: "k_axk16", 5: "k_axk_x6
             7: "k_dw_fin", 8: "k_heads_sample", 9: "k_gemm_sample_bwd", 10: "k_mt_sample",
             11: "k_gather", 12: "k_per_f1", 13: "k_per_f2", 14: "k_per_f2b", 15: "k_per_f3",
             16: "k_per_f4", 17: "per_unfused", 18: "k_adam", 19: "k_sample_bwd_tail",
-            20: "k_fwd16p", 21: "k_dw_part_x6"}
+            20: "k_fwd16p", 21: "k_dw_part_x6", 22: "k_per_feedback"}
 EXPORTS = tuple(_PROTOS) + ("sacmi_abi_version", "sacmi_last_error")
 
 _lib = None

@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 from .core import Config, Context, net_keys
 from .networks import MODELS
-from .replay import ReplayBuffer
+from .replay import PrioritizedReplayBuffer, ReplayBuffer
 
 _OPT_NETS = ("policy", "q1", "q2")
 
@@ -128,8 +128,17 @@ class SAC:
                  alpha=0.2, automatic_entropy_tuning=True, device=None, *,
                  capacity: int = 1000000, max_batch: int = 4096, action_bounds=None,
                  seed: int | None = None, sync_python_random: bool = False,
-                 networks: str = "model1", compute_dtype: str = "fp32"):
-        """``networks``: "model1" (networks_model1, the reference's import at
+                 networks: str = "model1", compute_dtype: str = "fp32",
+                 prioritized_replay: bool = False, per_alpha: float = 0.6,
+                 per_beta_start: float = 0.4, per_beta_frames: int = 100000):
+        """``prioritized_replay``: the agent owns a prioritized buffer
+        (``PrioritizedReplayBuffer(capacity, per_alpha, per_beta_start, per_beta_frames)``,
+        replay_buffer.py:25-90) and every update is the closed loop on the GPU: the batch is
+        drawn by priority, the critic losses carry the importance-sampling weights, and the
+        rows' TD errors 0.5 (|q1 - q^| + |q2 - q^|) come back as their priorities
+        (``update_priorities``) inside the update.  The device's numpy-MT stream starts at
+        ``np.random``'s state.
+        ``networks``: "model1" (networks_model1, the reference's import at
         sac_imp.py:4) or "model2" (networks_model2: three hidden layers, orthogonal
         policy init — the swap the reference makes by editing that import).
         ``compute_dtype``: "fp32" (the reference's arithmetic) or "bf16" (bf16 MFMA
@@ -156,7 +165,9 @@ class SAC:
                            tau=tau, lr=lr, alpha=float(alpha),
                            automatic_entropy_tuning=automatic_entropy_tuning,
                            action_low=lo, action_high=hi, capacity=capacity, seed=seed,
-                           n_hidden=QNetwork.n_hidden, compute_dtype=compute_dtype)
+                           n_hidden=QNetwork.n_hidden, compute_dtype=compute_dtype,
+                           **(dict(replay="per", per_alpha=per_alpha, per_beta_start=per_beta_start,
+                                   per_beta_frames=per_beta_frames) if prioritized_replay else {}))
         self._ctx = Context(self._cfg, _device_index(device))
         self._mods = {"policy": policy, "q1": q1, "q2": q2, "q1_target": q1_target,
                       "q2_target": q2_target}
@@ -170,8 +181,16 @@ class SAC:
         if automatic_entropy_tuning:
             self.target_entropy = -action_dim
             self.alpha_optimizer = _AdamMirror([self._log_alpha], lr, self, "alpha")
-        self.replay_buffer = ReplayBuffer(capacity, ctx=self._ctx,
-                                          sync_python_random=sync_python_random)
+        if prioritized_replay:
+            self._ctx.per_set_feedback(True)
+            self.replay_buffer = PrioritizedReplayBuffer(capacity, per_alpha, per_beta_start,
+                                                         per_beta_frames, ctx=self._ctx,
+                                                         sync_numpy_random=False)
+            nst = np.random.get_state()    # device prioritized draws start at np.random's stream
+            self._ctx.set_mt(1, nst[1], nst[2])
+        else:
+            self.replay_buffer = ReplayBuffer(capacity, ctx=self._ctx,
+                                              sync_python_random=sync_python_random)
         st = random.getstate()             # device sampling stream starts at `random`'s
         self._ctx.set_mt(0, np.array(st[1][:624], np.uint32), st[1][624])
         self._mt_adopted = st[1]           # (the Python stream state the device holds)
@@ -233,7 +252,9 @@ class SAC:
             raise ValueError("Sample larger than population or is negative")
         rb = self.replay_buffer
         self._stale = True     # (also when it raises: the critic step may have been taken)
-        if rb.sync_python_random and batch_size <= 4096 and self._ctx.cfg.replay == "uniform":
+        if self._ctx.cfg.replay != "uniform":
+            out = self._ctx.step(batch_size)      # (its draws: the device's numpy-MT stream)
+        elif rb.sync_python_random and batch_size <= 4096:
             st = random.getstate()
             if st[1] != self._mt_adopted:   # the stream moved (drawn from, seeded): adopt it
                 self._ctx.set_mt(0, np.array(st[1][:624], np.uint32), st[1][624])
@@ -274,13 +295,13 @@ class SAC:
         self._flush_device()
         if len(self.replay_buffer) < batch_size:
             raise ValueError("Sample larger than population or is negative")
-        rb = self.replay_buffer
-        if rb.sync_python_random:
+        sync = getattr(self.replay_buffer, "sync_python_random", False)
+        if sync:
             st = random.getstate()
             self._ctx.set_mt(0, np.array(st[1][:624], np.uint32), st[1][624])
         self._stale = True
         self._ctx.step_many_async(batch_size, n_updates)
-        if rb.sync_python_random:
+        if sync:
             key, pos = self._ctx.get_mt(0)
             random.setstate((3, tuple(int(x) for x in key) + (pos,), st[2]))
         # raises ValueError at the first update whose policy sample was NaN (the loop of

@@ -375,6 +375,24 @@ class Context:
         p = np.ascontiguousarray(prio, np.float32)
         L.call("sacmi_per_set_priorities", self._h, L.fptr(p), p.size)
 
+    def per_set_feedback(self, on: bool = True) -> None:
+        """Feedback mode (sacmi.h sacmi_per_set_feedback): device-sampled updates weight the
+        critic losses with the draw's importance-sampling weights and write the rows' TD errors
+        back as their priorities, on the device."""
+        L.call("sacmi_per_set_feedback", self._h, 1 if on else 0)
+
+    def per_feedback(self) -> bool:
+        out = ctypes.c_int32()
+        L.call("sacmi_per_feedback", self._h, ctypes.byref(out))
+        return bool(out.value)
+
+    def read_per_feedback(self, batch: int):
+        """(weights, td, stored) float32 [batch] of the last device-sampled update of `batch`
+        rows in batch set 0 (sacmi.h sacmi_read_per_feedback)."""
+        w, td, pv = (np.zeros(batch, np.float32) for _ in range(3))
+        L.call("sacmi_read_per_feedback", self._h, int(batch), L.fptr(w), L.fptr(td), L.fptr(pv))
+        return w, td, pv
+
     # -- diagnostics -------------------------------------------------------------------
     def profile_step(self, batch: int, iters: int = 10):
         """[(site, mean_ms, flops_per_launch)] over `iters` eager updates (HIP events)."""

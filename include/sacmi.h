@@ -340,6 +340,28 @@ int sacmi_per_sample(sacmi_ctx* ctx, int32_t batch, const double* u, int64_t* id
  * (replay_buffer.py:87; the +1e-6 is a double add, done host-side). */
 int sacmi_per_update(sacmi_ctx* ctx, const int64_t* idx, const float* values, int64_t n);
 int sacmi_per_get_priorities(sacmi_ctx* ctx, float* out, int64_t n);
+/* Feedback mode of a prioritized context (off at creation; SACMI_ESTATE on a uniform one).
+ * On, every device-sampled update is the loop a user would write against the buffer API:
+ *     s, a, r, s2, d, idx, w = buffer.sample(B)
+ *     q_i_loss = mean(w * (q_i(s, a) - q^) ** 2)           i = 1, 2
+ *     td       = 0.5 * (|q1 - q^| + |q2 - q^|)             fp32, per row
+ *     buffer.update_priorities(idx, td)                    stored: float32(float64(td) + 1e-6)
+ * with the write-back on the device, inside the update (last duplicate wins; the actor and
+ * alpha blocks are not weighted; the q losses returned are the weighted ones).  An update
+ * voided by a non-finite sample (SACMI_ENAN) writes no priority; a non-finite td is written
+ * as it is, and the next draw reports "probabilities contain NaN" (inside a multi-update launch
+ * that draw runs beside the update that produced the td, whose remaining steps may or may
+ * not stand: n updates in one launch equal n launches bit for bit for finite td only).  With
+ * feedback on, an update with staged indices, the phase-split updates and sacmi_step_dp return
+ * SACMI_ESTATE before they touch any state.
+ * Additive: the ABI version is unchanged. */
+int sacmi_per_set_feedback(sacmi_ctx* ctx, int32_t on);
+int sacmi_per_feedback(sacmi_ctx* ctx, int32_t* on);
+/* Test hook (feedback mode), for the last device-sampled update of `batch` rows on batch set
+ * 0 (as sacmi_read_batch): the importance-sampling weights it used, the td it computed and
+ * the priorities it stored, [batch] each (any may be NULL). */
+int sacmi_read_per_feedback(sacmi_ctx* ctx, int32_t batch, float* weights, float* td,
+                            float* stored);
 int sacmi_per_set_priorities(sacmi_ctx* ctx, const float* in, int64_t n);
 
 /* ---- action selection (sac_imp.py:54-72) ----------------------------------------- */
