@@ -1422,7 +1422,9 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
         float c = ok ? v * s_dotw[col] : 0.f;
         c = row16_sum(c);                 // DPP within each 16-lane row
         c += __shfl_xor(c, 16, 64);       // the two rows of the half wave
-        if ((tid & 31) == 0 && m0 + row < d.M)   // block 0 adds the bias: q = sum of blocks
+        // (ok: the row AND the block exist — a 64-column tile over N % 64 == 32 has a second
+        // block past N, whose slot (dotp_ld = N / 32 blocks a row) is the next row's block 0)
+        if ((tid & 31) == 0 && ok)   // block 0 adds the bias: q = sum of blocks
           st_pol(d.dotp + (size_t)(m0 + row) * d.dotp_ld + (n0 + col) / 32, n0 + col == 0 ? c + dotb_x : c, wt);
       }
     }

@@ -272,6 +272,13 @@ struct sacmi_ctx {
   sacmi::DevBuf<int64_t> per_q, per_blk, per_idx;
   sacmi::DevBuf<double> per_cdf, per_u, per_uin;
   sacmi::DevBuf<int32_t> per_owner, per_bad;
+  // sacmi_set_stats: every update appends one row of diagnostics (stats.hip) to stats_ring
+  // [kStatRingSlots][SACMI_STAT_COUNT]; stats_cnt: rows appended since creation; stats_ws: the
+  // workgroup partials of batches past kStatOneWgRows (allocated when first switched on)
+  sacmi::DevBuf<float> stats_ring;
+  sacmi::DevBuf<int64_t> stats_cnt;
+  sacmi::DevBuf<double> stats_ws;
+  bool stats_on = false;
   std::map<sacmi::GraphKey, hipGraphExec_t> graphs;
   bool use_graphs = true;
   bool G_external = false;
@@ -985,6 +992,38 @@ static void enqueue_feedback(sacmi_ctx* c, int B, const BatchBufs& bb, hipStream
   launch_per_feedback(f, s);
 }
 
+// The diagnostics buffers exist from the first time stats are switched on: a context that
+// never asks for them allocates what it always did.
+static void stats_alloc(sacmi_ctx* c) {
+  if (c->stats_ring.p) return;
+  c->stats_ring.alloc((size_t)kStatRingSlots * SACMI_STAT_COUNT);
+  c->stats_cnt.alloc(1);
+  c->stats_ws.alloc((size_t)stats_workgroups(c->Bm) * kStatAcc);
+}
+
+// The update's diagnostics row (sacmi_set_stats) on the main stream: behind the last L8 level
+// (the updated critics' head partials, slots 4 / 5, exist) and before the alpha step, which
+// overwrites DevScalars::alpha and log_alpha.  bb: the update's own batch set (its r, d).
+static void enqueue_stats(sacmi_ctx* c, int B, const BatchBufs& bb, hipStream_t s) {
+  if (!mark(c, "update_stats")) return;
+  StatsArgs a{};
+  a.dotp = c->dotp.p; a.nparts = c->nparts; a.B = B; a.logp = c->logp.p;
+  a.r = bb.r; a.d = bb.d; a.sc = c->sc.p; a.log_alpha = c->P.p + c->la_idx;
+  a.gamma = (float)c->cfg.gamma; a.target_entropy = (float)(-c->A);
+  a.auto_entropy = c->cfg.auto_entropy ? 1 : 0;
+  a.ring = c->stats_ring.p; a.count = c->stats_cnt.p; a.ws = c->stats_ws.p; a.tl = c->tl_cur;
+  check_span(a.dotp, (int64_t)6 * B * c->nparts - 1, "stats dotp");
+  check_span(a.logp, (int64_t)2 * B - 1, "stats logp");
+  check_span(a.r, B - 1, "stats r");
+  check_span(a.d, B - 1, "stats d");
+  check_span(a.sc, 0, "stats scalars", (int)sizeof(DevScalars));
+  check_span(a.log_alpha, 0, "stats log_alpha");
+  check_span(a.ring, (int64_t)kStatRingSlots * SACMI_STAT_COUNT - 1, "stats ring");
+  check_span(a.count, 0, "stats counter", 8);
+  check_span(a.ws, (int64_t)stats_workgroups(B) * kStatAcc - 1, "stats workspace", 8);
+  launch_update_stats(a, s);
+}
+
 // Feedback mode, update r of a multi-update graph that has a successor, called once r's L5 is
 // enqueued: the side stream forks here, writes update r's priorities back, then draws and
 // gathers update r + 1's batch (into the other set); update r + 1 joins on side_ev[2r + 3].
@@ -1355,6 +1394,8 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
     {
       run(l7, "gemm_L7_act_fc1");
       for (size_t i = 0; i < l8s.size(); ++i) run(l8s[i], i == 0 ? "gemm_L8_act_fc2" : "gemm_L8b_act_fc3");
+      // (no side-stream fork: every cross-stream edge cost the chain ~10 us, enqueue_many)
+      if (c->stats_on) enqueue_stats(c, B, bb, s);
       run(l9, "gemm_L9_act_dh1");
       for (Level& lv : l9bs) run(lv, "gemm_L9b_act_dh");
       if (fold_dlda) {
@@ -1504,7 +1545,8 @@ static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_
   GraphKey key{B, dev_idx, dev_eps,
                phase_mask | (grad_scale != 1.f ? 8 : 0) | (c->keep_grads ? 16 : 0) |
                    (pr.parity ? 32 : 0) | (pr.have_batch ? 64 : 0) | (pr.ride_next ? 128 : 0) |
-                   (c->mb_graph ? 256 : 0) | (c->per_feedback ? 512 : 0),
+                   (c->mb_graph ? 256 : 0) | (c->per_feedback ? 512 : 0) |
+                   (c->stats_on ? 1024 : 0),
                use_ring ? c->ring_slots : 0,
                per_graph_len(c), reps};
   auto it = c->graphs.find(key);
@@ -1939,6 +1981,11 @@ int sacmi_create(const sacmi_config* cfg, int device, sacmi_ctx** out) {
     CHECK_HIP(hipMemcpy(c->mt.p + 625, k.data(), 625 * 4, hipMemcpyHostToDevice));
     const char* ng = getenv("SACMI_NO_GRAPH");
     c->use_graphs = !(ng && ng[0] == '1');
+    // SACMI_STATS=1: diagnostics on from creation (sacmi_set_stats), for measuring their cost
+    // under a driver that does not know them
+    const char* st = getenv("SACMI_STATS");
+    c->stats_on = st && st[0] == '1';
+    if (c->stats_on) stats_alloc(c.get());
     *out = c.release();
   });
 }
@@ -1974,6 +2021,7 @@ int sacmi_destroy(sacmi_ctx* c) {
     c->idx32b.release(); c->idx64b.release();
     c->per_q.release(); c->per_blk.release(); c->per_idx.release(); c->per_cdf.release();
     c->per_u.release(); c->per_uin.release(); c->per_owner.release(); c->per_bad.release();
+    c->stats_ring.release(); c->stats_cnt.release(); c->stats_ws.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);
@@ -2599,6 +2647,49 @@ int sacmi_fetch_losses(sacmi_ctx* c, float* out, int32_t max_steps, int32_t* n_o
       throw Error{SACMI_ENAN, nan_message(c, h.err, c->Bm, " at update #" + std::to_string(h.loss_ring_pos) +
                                                               " of this agent (0-based; later updates of that launch were skipped)")};
     }
+  });
+}
+
+int sacmi_set_stats(sacmi_ctx* c, int32_t on) {
+  return guard([&] {
+    REQUIRE(c, SACMI_EVALUE, "null ctx");
+    pf_touch(c);
+    if (c->stats_on != (on != 0)) {   // (the data-parallel graphs carry no such key)
+      for (auto& kv : c->dp_graphs) (void)hipGraphExecDestroy(kv.second);
+      c->dp_graphs.clear();
+    }
+    if (on) stats_alloc(c);
+    c->stats_on = on != 0;           // (part of the graph key: both forms stay captured)
+  });
+}
+
+int sacmi_stats(sacmi_ctx* c, int32_t* on) {
+  return guard([&] {
+    REQUIRE(c && on, SACMI_EVALUE, "null argument");
+    *on = c->stats_on ? 1 : 0;
+  });
+}
+
+int sacmi_fetch_stats(sacmi_ctx* c, float* out, int32_t max_rows, int32_t* n_out, int64_t* total) {
+  return guard([&] {
+    REQUIRE(c && n_out, SACMI_EVALUE, "null argument");
+    REQUIRE(max_rows >= 0 && (max_rows == 0 || out), SACMI_EVALUE, "bad output buffer");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    int64_t cnt = 0;        // (never switched on: no buffers, no rows)
+    if (c->stats_cnt.p) CHECK_HIP(hipMemcpy(&cnt, c->stats_cnt.p, 8, hipMemcpyDeviceToHost));
+    const int64_t n = std::min<int64_t>(std::min<int64_t>(cnt, kStatRingSlots), max_rows);
+    // most recent n rows, oldest first: at most two contiguous runs of the ring
+    const int64_t first = (cnt - n) % kStatRingSlots;
+    const int64_t run1 = std::min<int64_t>(n, kStatRingSlots - first);
+    const size_t rowb = (size_t)SACMI_STAT_COUNT * 4;
+    if (run1 > 0)
+      CHECK_HIP(hipMemcpy(out, c->stats_ring.p + first * SACMI_STAT_COUNT, (size_t)run1 * rowb,
+                          hipMemcpyDeviceToHost));
+    if (n > run1)
+      CHECK_HIP(hipMemcpy(out + run1 * SACMI_STAT_COUNT, c->stats_ring.p, (size_t)(n - run1) * rowb,
+                          hipMemcpyDeviceToHost));
+    *n_out = (int32_t)n;
+    if (total) *total = cnt;
   });
 }
 

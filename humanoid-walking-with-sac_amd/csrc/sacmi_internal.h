@@ -111,7 +111,7 @@ enum TlKind : int {
   TL_GEMM = 1, TL_FWD_X6, TL_FWD16, TL_AXK16, TL_AXK_X6, TL_DW_PART16, TL_DW_FIN, TL_HEADS,
   TL_SAMPLE_BWD, TL_MT_SAMPLE, TL_GATHER, TL_PER_F1, TL_PER_F2, TL_PER_F2B, TL_PER_F3,
   TL_PER_F4, TL_PER_UNFUSED, TL_ADAM, TL_SAMPLE_TAIL, TL_FWD16P, TL_DW_PART_X6,
-  TL_PER_FEEDBACK, TL_KINDS
+  TL_PER_FEEDBACK, TL_UPDATE_STATS, TL_KINDS
 };
 constexpr int kTlEnd = 4;            // first of the ~end slots
 constexpr int kTlEndSlots = 4096;
@@ -655,5 +655,33 @@ struct PerFeedbackArgs {
   tl_word* tl;
 };
 void launch_per_feedback(const PerFeedbackArgs& a, hipStream_t s);
+
+// Per-update training diagnostics (stats.hip; sacmi_set_stats): one row of SACMI_STAT_COUNT
+// floats per update, reduced from what the update's forward passes left in HBM, appended to a
+// ring of kStatRingSlots rows.  Batches up to kStatOneWgRows: one launch of one workgroup;
+// larger (staged indices): one workgroup per kStatThreads rows leaves kStatAcc fp64 partials
+// each in `ws`, and a one-workgroup finish launch folds them in index order.
+constexpr int kStatRingSlots = 4096;
+constexpr int kStatThreads = 1024;
+constexpr int kStatOneWgRows = 4096;
+constexpr int kStatAcc = 9;          // eight fp64 sums and the TD maximum
+struct StatsArgs {
+  const float* dotp;        // [6][B][nparts] head dot partials (slots 0-5)
+  int nparts, B;
+  const float* logp;        // [2B]: log pi(a'|s') then log pi(a~|s)
+  const float* r; const float* d;   // [B] of the update's batch set
+  const DevScalars* sc;     // alpha (before this update's alpha step), err
+  const float* log_alpha;   // in the parameter arena (before this update's alpha step)
+  float gamma, target_entropy;
+  int auto_entropy;
+  float* ring;              // [kStatRingSlots][SACMI_STAT_COUNT]
+  int64_t* count;           // rows appended since creation
+  double* ws;               // [workgroups][kStatAcc] (batches past kStatOneWgRows)
+  tl_word* tl;              // two launches at most
+};
+inline int stats_workgroups(int B) {
+  return B <= kStatOneWgRows ? 1 : (B + kStatThreads - 1) / kStatThreads;
+}
+void launch_update_stats(const StatsArgs& a, hipStream_t s);
 
 }  // namespace sacmi

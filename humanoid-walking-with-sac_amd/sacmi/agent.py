@@ -130,8 +130,12 @@ class SAC:
                  seed: int | None = None, sync_python_random: bool = False,
                  networks: str = "model1", compute_dtype: str = "fp32",
                  prioritized_replay: bool = False, per_alpha: float = 0.6,
-                 per_beta_start: float = 0.4, per_beta_frames: int = 100000):
-        """``prioritized_replay``: the agent owns a prioritized buffer
+                 per_beta_start: float = 0.4, per_beta_frames: int = 100000,
+                 diagnostics: bool = False):
+        """``diagnostics``: every update also leaves one row of training diagnostics on the
+        device (``sacmi.STAT_NAMES``: mean Q values, TD error, entropy, alpha, ...), read with
+        ``fetch_diagnostics()``; what ``update_parameters*`` return does not change.
+        ``prioritized_replay``: the agent owns a prioritized buffer
         (``PrioritizedReplayBuffer(capacity, per_alpha, per_beta_start, per_beta_frames)``,
         replay_buffer.py:25-90) and every update is the closed loop on the GPU: the batch is
         drawn by priority, the critic losses carry the importance-sampling weights, and the
@@ -191,6 +195,8 @@ class SAC:
         else:
             self.replay_buffer = ReplayBuffer(capacity, ctx=self._ctx,
                                               sync_python_random=sync_python_random)
+        if diagnostics:
+            self._ctx.set_stats(True)
         st = random.getstate()             # device sampling stream starts at `random`'s
         self._ctx.set_mt(0, np.array(st[1][:624], np.uint32), st[1][624])
         self._mt_adopted = st[1]           # (the Python stream state the device holds)
@@ -313,6 +319,12 @@ class SAC:
         rows = self._ctx.fetch_losses(max_steps)
         return [{"q1_loss": float(r[0]), "q2_loss": float(r[1]), "policy_loss": float(r[2])}
                 for r in rows]
+
+    def fetch_diagnostics(self, max_rows=4096):
+        """The most recent updates' diagnostics rows, oldest first, as dicts keyed by
+        ``sacmi.STAT_NAMES`` ([] unless the agent was built with ``diagnostics=True``)."""
+        rows, _ = self._ctx.fetch_stats(max_rows)
+        return [{k: float(v) for k, v in zip(L.STAT_NAMES, r)} for r in rows]
 
     def select_action(self, state, evaluate=False):
         """sac_imp.py:54-72: tanh(mean) when evaluating, a policy sample otherwise."""

@@ -251,6 +251,26 @@ class Context:
         L.call("sacmi_fetch_losses", self._h, L.fptr(out), int(max_steps), ctypes.byref(n))
         return out[:n.value]
 
+    def set_stats(self, on: bool = True) -> None:
+        """Per-update diagnostics (sacmi.h sacmi_set_stats): on, every update appends one row
+        of ``L.STAT_NAMES`` values, reduced on the device, to a ring of 4096 rows."""
+        L.call("sacmi_set_stats", self._h, 1 if on else 0)
+
+    def stats(self) -> bool:
+        out = ctypes.c_int32()
+        L.call("sacmi_stats", self._h, ctypes.byref(out))
+        return bool(out.value)
+
+    def fetch_stats(self, max_rows: int = 4096):
+        """(rows float32 [n, 12], total): the most recent min(total, 4096, max_rows) rows,
+        oldest first, and the rows appended since creation.  Synchronises; reports no error."""
+        out = np.zeros((max(int(max_rows), 0), L.STAT_COUNT), np.float32)
+        n = ctypes.c_int32()
+        total = ctypes.c_int64()
+        L.call("sacmi_fetch_stats", self._h, L.fptr(out) if out.size else None, out.shape[0],
+               ctypes.byref(n), ctypes.byref(total))
+        return out[:n.value], int(total.value)
+
     def step_phase(self, batch: int, phase: int, grad_scale: float = 1.0, parity: int = 0,
                    have_batch: bool = False, ride_next: bool = False) -> None:
         if parity or have_batch or ride_next:

@@ -213,6 +213,46 @@ int sacmi_step_async(sacmi_ctx* ctx, int32_t batch);
 int sacmi_step_many_async(sacmi_ctx* ctx, int32_t batch, int32_t n_updates);
 int sacmi_fetch_losses(sacmi_ctx* ctx, float* out, int32_t max_steps, int32_t* n_out);
 
+/* ---- per-update training diagnostics ------------------------------------------------- */
+/* Off at creation.  On, every update — fused or phase-split, synchronous, async or inside a
+ * multi-update launch, staged or device-sampled indices, data parallel (the rank's own
+ * minibatch: no collective is added) — appends one row of SACMI_STAT_COUNT fp32 values to a
+ * device ring of 4096 rows, reduced on the device from what the update's forward passes left
+ * in HBM (one more one-workgroup launch in the actor block, behind the forward of the updated
+ * critics and before the alpha step).  Over the B rows i of the update's minibatch:
+ *   Q1_MEAN, Q2_MEAN  mean q1(s_i, a_i), mean q2(s_i, a_i) (the critics before their step)
+ *   Q_TARGET_MEAN     mean q^_i, q^ = r + (1 - d) gamma (min(q1t, q2t)(s', a') - alpha log pi(a'|s'))
+ *                     (sac_imp.py:87-98)
+ *   TD_MEAN, TD_MAX   mean / max of 0.5 (|q1 - q^| + |q2 - q^|): unweighted, also under
+ *                     prioritized feedback
+ *   Q_PI_MEAN         mean min(q1, q2)(s_i, a~_i) with the critics AFTER this update's critic
+ *                     step (sac_imp.py:117-119)
+ *   ENTROPY           -mean log pi(a~_i | s_i)
+ *   ALPHA, LOG_ALPHA  the temperature this update's losses used and log_alpha, both before this
+ *                     update's alpha step
+ *   ALPHA_LOSS        -log_alpha mean(log pi(a~|s) + target_entropy), target_entropy =
+ *                     -action_dim (sac_imp.py:128-131); 0 without automatic entropy tuning
+ *   REWARD_MEAN       mean r_i
+ *   BATCH             (float)B
+ * Per-row values are fp32; the sums accumulate in fp64 in a fixed order (no atomics: two runs
+ * from the same state give the same bits) and each mean is rounded once.  An update voided by
+ * a non-finite input (SACMI_ENAN; any error bit set when the reduction runs) appends nothing,
+ * as it returns no losses.  Off, the update's launches are exactly those of a context that
+ * never enabled it (the switch is part of the graph key).  SACMI_STATS=1 in the environment at
+ * sacmi_create switches it on from the start.
+ * Additive: the ABI version is unchanged. */
+enum sacmi_stat { SACMI_STAT_Q1_MEAN = 0, SACMI_STAT_Q2_MEAN = 1, SACMI_STAT_Q_TARGET_MEAN = 2,
+                  SACMI_STAT_TD_MEAN = 3, SACMI_STAT_TD_MAX = 4, SACMI_STAT_Q_PI_MEAN = 5,
+                  SACMI_STAT_ENTROPY = 6, SACMI_STAT_ALPHA = 7, SACMI_STAT_LOG_ALPHA = 8,
+                  SACMI_STAT_ALPHA_LOSS = 9, SACMI_STAT_REWARD_MEAN = 10, SACMI_STAT_BATCH = 11,
+                  SACMI_STAT_COUNT = 12 };
+int sacmi_set_stats(sacmi_ctx* ctx, int32_t on);
+int sacmi_stats(sacmi_ctx* ctx, int32_t* on);
+/* Synchronises the stream; copies the most recent min(total, 4096, max_rows) rows, oldest
+ * first ([n][SACMI_STAT_COUNT] f32); *total (may be NULL) = rows appended since creation.
+ * Read-only: reports and clears no error (sacmi_fetch_losses does that). */
+int sacmi_fetch_stats(sacmi_ctx* ctx, float* out, int32_t max_rows, int32_t* n_out, int64_t* total);
+
 /* Data-parallel split of the step (one process per GPU).  phase 0: sample, gather,
  * forward, critic backward -> critic gradient buffer; phase 1: critic Adam + Polyak,
  * actor forward/backward -> actor gradient buffer; phase 2: actor Adam + alpha;
