@@ -3793,7 +3793,14 @@ __device__ __forceinline__ float wave_sum(float v) {
 // kernels and no element reads what it writes — after block 0's elements it put a chain of
 // dependent round trips at the end of the kernel (the fused levels moved it the same way,
 // adam_block0_wave).  The element blocks are the grid's first gridDim.x - 1.
-__device__ __forceinline__ void adam_scalar_tail(const AdamArgs& a, float om_b1, float om_b2) {
+// Clipped form (AdamArgs::clip_part): gn = this launch's groups' {norm, coef} pairs from the
+// prologue.  The critic launch parks them; the actor launch, which ends the update, appends the
+// update's row to the norm ring — only here, where the update's losses are final: an update
+// that returns no losses (any error bit) never reaches this function.
+// A launch that stands in for a fused level also stores the level's losses to the host-mapped
+// words (loss_host), as the level's block 0 does.
+__device__ __forceinline__ void adam_scalar_tail(const AdamArgs& a, float om_b1, float om_b2,
+                                                 const float (*gn)[2]) {
   if (threadIdx.x == 0 && a.log_alpha_idx >= 0 && a.auto_entropy) {
     const AdamScalars k = adam_scalars(a, 3);
     const int64_t i = a.log_alpha_idx;
@@ -3809,6 +3816,8 @@ __device__ __forceinline__ void adam_scalar_tail(const AdamArgs& a, float om_b1,
     a.sc->losses[a.loss_slot0 + threadIdx.x] = s / a.loss_div;
   }
   __syncthreads();
+  if (threadIdx.x == 0 && a.loss_host)   // (thread 0: the one that stores the done word behind them)
+    for (int l = 0; l < a.n_losses; ++l) a.loss_host[a.loss_slot0 + l] = a.sc->losses[a.loss_slot0 + l];
   if (threadIdx.x == 0 && a.loss_ring) {
     const int64_t pos = a.sc->loss_ring_pos;
     const int64_t q = pos % a.ring;
@@ -3817,11 +3826,27 @@ __device__ __forceinline__ void adam_scalar_tail(const AdamArgs& a, float om_b1,
     a.loss_ring[q * 3 + 2] = a.sc->losses[2];
     a.sc->loss_ring_pos = pos + 1;
   }
+  if (threadIdx.x == 0 && a.clip_part) {
+    if (a.clip_group0 == 0) {
+      a.clip->parked[0] = gn[0][0]; a.clip->parked[1] = gn[1][0];
+      a.clip->parked[2] = gn[0][1]; a.clip->parked[3] = gn[1][1];
+    } else {
+      const int64_t pos = a.clip->count;
+      float* row = a.gnorm_ring + (size_t)(pos % kGnormRingSlots) * SACMI_GNORM_COUNT;
+      row[SACMI_GNORM_Q1] = a.clip->parked[0]; row[SACMI_GNORM_Q2] = a.clip->parked[1];
+      row[SACMI_GNORM_PI] = gn[0][0];
+      row[SACMI_GCOEF_Q1] = a.clip->parked[2]; row[SACMI_GCOEF_Q2] = a.clip->parked[3];
+      row[SACMI_GCOEF_PI] = gn[0][1];
+      a.clip->count = pos + 1;
+    }
+  }
 }
 
 __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
   const TlMark tl_mark(a.tl, TL_ADAM);
   __shared__ AdamScalars s_k[kMaxAdamSegs];
+  __shared__ float s_coef[kMaxAdamSegs];      // per segment, next to s_k (clipped form)
+  __shared__ float s_gn[kClipMaxGroups][2];   // per group of this launch: norm, coef
   __shared__ int64_t s_prefix[kMaxAdamSegs + 1];
   __shared__ int s_err;
   if (threadIdx.x < a.nseg) s_k[threadIdx.x] = adam_scalars(a, a.seg[threadIdx.x].step_idx);
@@ -3840,6 +3865,26 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
     }
     s_err = err;
   }
+  if (a.clip_part) {
+    // the finish of k_grad_sumsq, in every workgroup: the group's partials in index order in
+    // fp64 (the same bits everywhere), then norm and coef in fp32.  One thread per group, on
+    // wave 1 (wave 0's thread 0 has the prefix and the error word)
+    const int k = (int)threadIdx.x - kWave;
+    if (k >= 0 && k < a.clip_ngroups) {
+#ifdef SACMI_CLIP_SEPARATE_FINISH   // (the A/B of DESIGN §19: a one-wave finish launch did this)
+      s_gn[k][0] = a.clip->fin[a.clip_group0 + k][0];
+      s_gn[k][1] = a.clip->fin[a.clip_group0 + k][1];
+#else
+      double sum = a.clip_part[a.clip_wg_begin[k]];
+      for (int w = a.clip_wg_begin[k] + 1; w < a.clip_wg_begin[k + 1]; ++w) sum += a.clip_part[w];
+      const float norm = (float)sqrt(sum);
+      s_gn[k][0] = norm;
+      s_gn[k][1] = clip_coef(norm, a.clip->max_norm[a.clip_group0 + k]);
+#endif
+    }
+    __syncthreads();
+    if (threadIdx.x < a.nseg) s_coef[threadIdx.x] = s_gn[a.seg_group[threadIdx.x]][1];
+  }
   __syncthreads();
   const float om_b1 = 1.f - a.beta1, om_b2 = 1.f - a.beta2, omtau = 1.f - a.tau;
   // a non-finite policy sample / PER draw of this update (ErrBits, see k_gemm): no step,
@@ -3847,11 +3892,21 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
   const int err = s_err;
   const unsigned nel = gridDim.x - 1;   // element workgroups; the last one: the scalar work
   if (blockIdx.x == nel) {
-    if (!err) adam_scalar_tail(a, om_b1, om_b2);
+    if (!err) adam_scalar_tail(a, om_b1, om_b2, s_gn);
+    // (voided updates too: the error bits for the synchronous step's readback, and the done
+    // word the host waits on — behind every other host-mapped store of this thread)
+    if (threadIdx.x == 0 && a.loss_host) a.loss_host[3] = __int_as_float(err);
+    if (threadIdx.x == 0 && a.done_word) {
+      const int v = a.sc->done_seq + 1;
+      a.sc->done_seq = v;
+      __threadfence_system();
+      *reinterpret_cast<volatile int*>(a.done_word) = v;
+    }
     return;
   }
   if (err & a.err_skip) return;
   const bool pol = a.tgt && (err & a.err_nopolyak) == 0;
+  const bool clip = a.clip_part != nullptr;
   const int64_t total4 = s_prefix[a.nseg];
   // parameter / moment / target arenas: one descriptor each (offsets < 2 GiB: the arenas
   // hold at most a few million floats)
@@ -3873,6 +3928,10 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
     // would wait for them), through a zero-length range where there is none
     float4 t = buf_ld4(rT, a.tgt ? (uint32_t)(i - a.tgt_base) * 4u : 0u);
     g.x *= a.grad_scale; g.y *= a.grad_scale; g.z *= a.grad_scale; g.w *= a.grad_scale;
+    if (clip) {   // (g * grad_scale) * coef: a rounded product of its own (x * 1.0f is exact)
+      const float cf = s_coef[sg];
+      g.x *= cf; g.y *= cf; g.z *= cf; g.w *= cf;
+    }
     adam_elem(p.x, m.x, v.x, g.x, om_b1, a.beta2, om_b2, a.eps, k);
     adam_elem(p.y, m.y, v.y, g.y, om_b1, a.beta2, om_b2, a.eps, k);
     adam_elem(p.z, m.z, v.z, g.z, om_b1, a.beta2, om_b2, a.eps, k);

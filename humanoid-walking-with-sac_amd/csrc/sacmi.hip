@@ -279,6 +279,16 @@ struct sacmi_ctx {
   sacmi::DevBuf<int64_t> stats_cnt;
   sacmi::DevBuf<double> stats_ws;
   bool stats_on = false;
+  // sacmi_set_grad_clip: the thresholds, the parked critic values and the row counter on the
+  // device (clip_state), the fp64 workgroup partials of k_grad_sumsq (clip_part: q1's, q2's,
+  // then the policy's; clip_wgs each, constant for the context) and the norm-record ring
+  // [kGnormRingSlots][SACMI_GNORM_COUNT]; allocated when first switched on
+  sacmi::DevBuf<sacmi::ClipState> clip_state;
+  sacmi::DevBuf<double> clip_part;
+  sacmi::DevBuf<float> gnorm_ring;
+  int clip_wgs[3] = {};
+  bool clip_on = false;
+  double clip_max[2] = {};             // effective thresholds (critic, actor) while on
   std::map<sacmi::GraphKey, hipGraphExec_t> graphs;
   bool use_graphs = true;
   bool G_external = false;
@@ -1024,6 +1034,71 @@ static void enqueue_stats(sacmi_ctx* c, int B, const BatchBufs& bb, hipStream_t 
   launch_update_stats(a, s);
 }
 
+// The clipping buffers exist from the first time the feature is switched on (as stats_alloc).
+// The workgroup count of each group follows from its size and stays what it is.
+static void clip_alloc(sacmi_ctx* c) {
+  if (c->clip_state.p) return;
+  int64_t n[3] = {0, 0, 0};
+  for (int l = 0; l <= c->nh; ++l) {
+    n[0] += c->q_fc[0][l].numel_padded();
+    n[1] += c->q_fc[1][l].numel_padded();
+    n[2] += (l < c->nh ? c->p_fc[l] : c->p_head).numel_padded();
+  }
+  for (int k = 0; k < 3; ++k) c->clip_wgs[k] = clip_workgroups(n[k]);
+  c->clip_state.alloc(1);
+  c->clip_part.alloc((size_t)c->clip_wgs[0] + c->clip_wgs[1] + c->clip_wgs[2]);
+  c->gnorm_ring.alloc((size_t)kGnormRingSlots * SACMI_GNORM_COUNT);
+}
+
+// One range's optimizer step with clipping on: k_grad_sumsq over the range's real gradient
+// elements (the critic range's trailing kDpFlagN flag floats are no segment: never read), then
+// the Adam launch, whose prologue finishes the norms and applies the coefficients.  `ad`: the
+// step as dp_adam_args describes it (un-sharded: whole segments).
+static void enqueue_clip_adam(sacmi_ctx* c, AdamArgs ad, bool critic, const char* adam_name, hipStream_t s) {
+  GradSumsqArgs gs{};
+  gs.g = ad.g; gs.grad_scale = ad.grad_scale;
+  gs.clip = c->clip_state.p; gs.group0 = critic ? 0 : 2;
+  gs.ngroups = critic ? 2 : 1;
+  const int part0 = critic ? 0 : c->clip_wgs[0] + c->clip_wgs[1];
+  gs.part = c->clip_part.p + part0;
+  gs.wg_begin[0] = 0;
+  for (int k = 0; k < gs.ngroups; ++k) gs.wg_begin[k + 1] = gs.wg_begin[k] + c->clip_wgs[(critic ? 0 : 2) + k];
+  auto seg = [&](const Linear& l, int group) {
+    REQUIRE(gs.nseg < kMaxAdamSegs, SACMI_ESTATE, "too many clip segments");
+    REQUIRE(l.off % 4 == 0 && l.ld % 4 == 0 && l.kdim() <= l.ld, SACMI_ESTATE, "clip segment not float4-aligned");
+    check_span(gs.g + l.off, l.numel_padded() - 1, "clip gradient segment");
+    gs.seg[gs.nseg++] = ClipSeg{l.off, l.n_out, l.ld, l.kdim(), group};
+  };
+  // (the segments in dp_adam_args' order: the Adam launch's seg_group is the same list)
+  if (critic) {
+    for (int layer = 0; layer <= c->nh; ++layer)
+      for (int i = 0; i < 2; ++i) seg(c->q_fc[i][layer], i);
+  } else {
+    for (int l = 0; l <= c->nh; ++l) seg(l < c->nh ? c->p_fc[l] : c->p_head, 0);
+  }
+  REQUIRE(gs.nseg == ad.nseg, SACMI_ESTATE, "clip segments do not match the Adam step's");
+  for (int i = 0; i < gs.nseg; ++i) {
+    REQUIRE(gs.seg[i].off == ad.seg[i].off && (int64_t)gs.seg[i].rows * gs.seg[i].ld == ad.seg[i].n,
+            SACMI_ESTATE, "clip segments do not match the Adam step's");
+    ad.seg_group[i] = gs.seg[i].group;
+  }
+  check_span(gs.part, gs.wg_begin[gs.ngroups] - 1, "clip partials", 8);
+  check_span(c->clip_state.p, 0, "clip state", (int)sizeof(ClipState));
+  check_span(c->gnorm_ring.p, (int64_t)kGnormRingSlots * SACMI_GNORM_COUNT - 1, "grad norm ring");
+  if (mark(c, critic ? "grad_sumsq_critic" : "grad_sumsq_actor", 0, 4.0 * (double)ad.total)) {
+    gs.tl = c->tl_cur;
+    launch_grad_sumsq(gs, s);
+  }
+  ad.clip_part = gs.part; ad.clip_ngroups = gs.ngroups;
+  for (int k = 0; k <= gs.ngroups; ++k) ad.clip_wg_begin[k] = gs.wg_begin[k];
+  ad.clip_group0 = critic ? 0 : 2;
+  ad.clip = c->clip_state.p; ad.gnorm_ring = c->gnorm_ring.p;
+  if (mark(c, adam_name)) {
+    ad.tl = c->tl_cur;
+    launch_adam(ad, s);
+  }
+}
+
 // Feedback mode, update r of a multi-update graph that has a successor, called once r's L5 is
 // enqueued: the side stream forks here, writes update r's priorities back, then draws and
 // gathers update r + 1's batch (into the other set); update r + 1 joins on side_ev[2r + 3].
@@ -1120,7 +1195,10 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
     hs.logp_part = c->lp_part.p; hs.split_row = B;    // sums of log pi(a~|s) for dL/dlog_alpha
     // Normal validation of policy.sample(next_state) / policy.sample(state) (sac_imp.py:89,116)
     hs.nan_flag = &c->sc.p->err; hs.nan_bit_lo = ERR_NAN_TGT; hs.nan_bit_hi = ERR_NAN_ACT;
-    const bool fuse = phase_mask == 7;     // single-GPU update: Adam in the dW epilogues
+    // single-GPU update: Adam in the dW epilogues — unless the gradients are clipped: the norm
+    // needs the whole gradient before any of it is consumed, so the dW levels store to the arena
+    // (same reduction order, same bits) and the Adam steps follow in launches of their own
+    const bool fuse = phase_mask == 7 && !c->clip_on;
     // L5: dh[L-1] = (dh[L] W[L]) * relu'(h[L-1]), with the target / critic-loss rows folded
     // in: the row prologue finishes q1, q2, qt1, qt2 from the dot partials and gives
     // dq_i = 2 (q_i - q^) / B; the A operand dh[L] = dq * w_head * [h[L] > 0] is formed
@@ -1238,7 +1316,7 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
       l6.b.ride.tbl_log2 = mt_sample_tbl_log2(B, true);
       l6.b.ride.mt = mt_args(c, B, batch_bufs(c, parity ^ 1));
     }
-    if (!fuse) {   // data parallel: this update's error flags ride in the critic collective
+    if (phase_mask != 7) {   // data parallel: this update's error flags ride in the critic collective
       l6.b.err_flags = c->dp_sharding_now ? c->dp_flags.p : G + c->q_end;
       l6.b.err_word = &c->sc.p->err;
       check_span(l6.b.err_flags, kDpFlagN - 1, "error flags");
@@ -1246,12 +1324,19 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
     run(l6, fuse ? "gemm_L6_critic_dW_adam" : "gemm_L6_critic_dW1");
   }
   if (phase_mask & 2) {
-   const bool fuse = phase_mask == 7;
+   const bool fuse = phase_mask == 7 && !c->clip_on;
    if (!fuse && !c->dp_sharding_now) {   // (sharded: enqueue_dp takes the critic step)
     // critic Adam (+ Polyak, + q-loss finalisation)
     AdamArgs ad = dp_adam_args(c, true, B, grad_scale, use_ring);
     if (polyak_ride) { ad.tgt = nullptr; ad.tgth = nullptr; }   // (Polyak: in L12)
-    if (mark(c, polyak_ride ? "adam_critic" : "adam_critic_polyak")) {
+    if (phase_mask == 7) {   // the clipped single-GPU update: in L6's place (no collective, no
+      ad.err_flags = nullptr;             // flags; the early error word for the synchronous step)
+      ad.loss_host = c->loss_host_dev;
+    }
+    const char* name = polyak_ride ? "adam_critic" : "adam_critic_polyak";
+    if (c->clip_on) {
+      enqueue_clip_adam(c, ad, true, name, s);
+    } else if (mark(c, name)) {
       ad.tl = c->tl_cur;
       launch_adam(ad, s);
     }
@@ -1414,9 +1499,15 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
     // (off the chain in front of L6: nothing of this update reads the priorities)
     if (fb && fork_r < 0) enqueue_feedback(c, B, bb, s);
   }
-  if ((phase_mask & 4) && phase_mask != 7) {
+  if ((phase_mask & 4) && (phase_mask != 7 || c->clip_on)) {
     AdamArgs ad = dp_adam_args(c, false, B, grad_scale, use_ring);
-    if (mark(c, "adam_actor_alpha")) {
+    if (phase_mask == 7) {   // the clipped single-GPU update: in L13's place, the update's last
+      ad.loss_host = c->loss_host_dev;    // scalar work (the synchronous step's losses and done word)
+      ad.done_word = reinterpret_cast<int*>(c->loss_host_dev + 4);
+    }
+    if (c->clip_on) {
+      enqueue_clip_adam(c, ad, false, "adam_actor_alpha", s);
+    } else if (mark(c, "adam_actor_alpha")) {
       ad.tl = c->tl_cur;
       launch_adam(ad, s);
     }
@@ -1546,7 +1637,7 @@ static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_
                phase_mask | (grad_scale != 1.f ? 8 : 0) | (c->keep_grads ? 16 : 0) |
                    (pr.parity ? 32 : 0) | (pr.have_batch ? 64 : 0) | (pr.ride_next ? 128 : 0) |
                    (c->mb_graph ? 256 : 0) | (c->per_feedback ? 512 : 0) |
-                   (c->stats_on ? 1024 : 0),
+                   (c->stats_on ? 1024 : 0) | (c->clip_on ? 2048 : 0),
                use_ring ? c->ring_slots : 0,
                per_graph_len(c), reps};
   auto it = c->graphs.find(key);
@@ -1935,6 +2026,8 @@ int sacmi_device_count(int* n) {
   return guard([&] { CHECK_HIP(hipGetDeviceCount(n)); });
 }
 
+static void set_grad_clip(sacmi_ctx* c, double mc, double ma);
+
 int sacmi_create(const sacmi_config* cfg, int device, sacmi_ctx** out) {
   return guard([&] {
     REQUIRE(cfg && out, SACMI_EVALUE, "null argument");
@@ -1986,6 +2079,22 @@ int sacmi_create(const sacmi_config* cfg, int device, sacmi_ctx** out) {
     const char* st = getenv("SACMI_STATS");
     c->stats_on = st && st[0] == '1';
     if (c->stats_on) stats_alloc(c.get());
+    // SACMI_GRAD_CLIP=<critic>[,<actor>]: clipping on from creation (sacmi_set_grad_clip), one
+    // value for both ranges, "inf" to measure only
+    if (const char* gc = getenv("SACMI_GRAD_CLIP")) {
+      char* end = nullptr;
+      const double mc = std::strtod(gc, &end);
+      REQUIRE(end != gc, SACMI_EVALUE, "SACMI_GRAD_CLIP: expected <critic>[,<actor>]");
+      double ma = mc;
+      if (*end == ',') {
+        const char* p2 = end + 1;
+        ma = std::strtod(p2, &end);
+        REQUIRE(end != p2, SACMI_EVALUE, "SACMI_GRAD_CLIP: expected <critic>[,<actor>]");
+      }
+      REQUIRE(*end == 0, SACMI_EVALUE, "SACMI_GRAD_CLIP: expected <critic>[,<actor>]");
+      set_grad_clip(c.get(), mc, ma);
+      CHECK_HIP(hipStreamSynchronize(c->stream));
+    }
     *out = c.release();
   });
 }
@@ -2022,6 +2131,7 @@ int sacmi_destroy(sacmi_ctx* c) {
     c->per_q.release(); c->per_blk.release(); c->per_idx.release(); c->per_cdf.release();
     c->per_u.release(); c->per_uin.release(); c->per_owner.release(); c->per_bad.release();
     c->stats_ring.release(); c->stats_cnt.release(); c->stats_ws.release();
+    c->clip_state.release(); c->clip_part.release(); c->gnorm_ring.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);
@@ -2693,6 +2803,73 @@ int sacmi_fetch_stats(sacmi_ctx* c, float* out, int32_t max_rows, int32_t* n_out
   });
 }
 
+// the sharded data-parallel optimizer step has each rank's chunk of the gradient only: the
+// group norms would need one more collective, which is not built
+static void refuse_clip_sharded(const sacmi_ctx* c, bool sharded) {
+  REQUIRE(!(c->clip_on && sharded), SACMI_ESTATE,
+          "gradient clipping is on: the sharded data-parallel optimizer step is not supported (its "
+          "norm needs a collective over the ranks' chunk sums, which is not built); use the "
+          "all-reduce form (sacmi_dp_set_sharded(0), SACMI_DP_SHARD unset) or sacmi_set_grad_clip(0, 0)");
+}
+static bool dp_active(const sacmi_ctx* c) { return c->comm || c->dp_loopback; }
+
+static void set_grad_clip(sacmi_ctx* c, double mc, double ma) {
+  REQUIRE(c, SACMI_EVALUE, "null ctx");
+  REQUIRE(mc >= 0.0 && ma >= 0.0, SACMI_EVALUE, "max_norm must be >= 0 or +inf (0: off / measured only)");
+  const bool on = mc > 0.0 || ma > 0.0;
+  REQUIRE(!(on && dp_active(c) && c->dp_shard), SACMI_ESTATE,
+          "gradient clipping needs the all-reduce data-parallel form (this context takes the sharded "
+          "optimizer step, whose norm would need one more collective: not built)");
+  pf_touch(c);
+  if (c->clip_on != on) {   // (the data-parallel graphs carry no such key)
+    for (auto& kv : c->dp_graphs) (void)hipGraphExecDestroy(kv.second);
+    c->dp_graphs.clear();
+  }
+  c->clip_on = on;            // (part of the graph key: both forms stay captured)
+  c->clip_max[0] = on ? (mc > 0.0 ? mc : INFINITY) : 0.0;
+  c->clip_max[1] = on ? (ma > 0.0 ? ma : INFINITY) : 0.0;
+  if (!on) return;
+  clip_alloc(c);
+  // stream-ordered: updates already enqueued keep the thresholds they were enqueued under
+  const float fc = (float)c->clip_max[0], fa = (float)c->clip_max[1];
+  launch_set_clip(c->clip_state.p, fc, fc, fa, c->stream);
+}
+
+int sacmi_set_grad_clip(sacmi_ctx* c, double max_norm_critic, double max_norm_actor) {
+  return guard([&] { set_grad_clip(c, max_norm_critic, max_norm_actor); });
+}
+
+int sacmi_grad_clip(sacmi_ctx* c, double* max_norm_critic, double* max_norm_actor) {
+  return guard([&] {
+    REQUIRE(c && max_norm_critic && max_norm_actor, SACMI_EVALUE, "null argument");
+    *max_norm_critic = c->clip_max[0];
+    *max_norm_actor = c->clip_max[1];
+  });
+}
+
+int sacmi_fetch_grad_norms(sacmi_ctx* c, float* out, int32_t max_rows, int32_t* n_out, int64_t* total) {
+  return guard([&] {
+    REQUIRE(c && n_out, SACMI_EVALUE, "null argument");
+    REQUIRE(max_rows >= 0 && (max_rows == 0 || out), SACMI_EVALUE, "bad output buffer");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    int64_t cnt = 0;        // (never switched on: no buffers, no rows)
+    if (c->clip_state.p)
+      CHECK_HIP(hipMemcpy(&cnt, &c->clip_state.p->count, 8, hipMemcpyDeviceToHost));
+    const int64_t n = std::min<int64_t>(std::min<int64_t>(cnt, kGnormRingSlots), max_rows);
+    const int64_t first = (cnt - n) % kGnormRingSlots;
+    const int64_t run1 = std::min<int64_t>(n, kGnormRingSlots - first);
+    const size_t rowb = (size_t)SACMI_GNORM_COUNT * 4;
+    if (run1 > 0)
+      CHECK_HIP(hipMemcpy(out, c->gnorm_ring.p + first * SACMI_GNORM_COUNT, (size_t)run1 * rowb,
+                          hipMemcpyDeviceToHost));
+    if (n > run1)
+      CHECK_HIP(hipMemcpy(out + run1 * SACMI_GNORM_COUNT, c->gnorm_ring.p, (size_t)(n - run1) * rowb,
+                          hipMemcpyDeviceToHost));
+    *n_out = (int32_t)n;
+    if (total) *total = cnt;
+  });
+}
+
 int sacmi_step_phase(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_scale) {
   return guard([&] {
     pf_touch(c);
@@ -2738,6 +2915,7 @@ int sacmi_allreduce_init(sacmi_ctx* c, const void* id, int32_t nbytes, int32_t r
     REQUIRE(id && nbytes == (int32_t)sizeof(ncclUniqueId), SACMI_EVALUE, "bad RCCL unique id");
     REQUIRE(world >= 1 && rank >= 0 && rank < world, SACMI_EVALUE, "bad rank / world");
     REQUIRE(!c->comm && !c->dp_loopback, SACMI_ESTATE, "communicator already initialised");
+    refuse_clip_sharded(c, dp_shard_default(world));
     CHECK_HIP(hipSetDevice(c->device));
     ncclUniqueId uid;
     std::memcpy(&uid, id, sizeof(uid));
@@ -2756,6 +2934,7 @@ int sacmi_dp_loopback_init(sacmi_ctx* c, int32_t world) {
     REQUIRE(c, SACMI_EVALUE, "null ctx");
     REQUIRE(world >= 1 && world <= 1024, SACMI_EVALUE, "world must be in [1, 1024]");
     REQUIRE(!c->comm, SACMI_ESTATE, "communicator already initialised");
+    refuse_clip_sharded(c, dp_shard_default(world));
     c->dp_world = world;
     c->dp_rank = 0;
     c->dp_loopback = true;
@@ -2766,6 +2945,7 @@ int sacmi_dp_loopback_init(sacmi_ctx* c, int32_t world) {
 
 int sacmi_step_dp(sacmi_ctx* c, int32_t batch, int32_t n_updates) {
   return guard([&] {
+    refuse_clip_sharded(c, c->dp_shard && (c->dp_world > 1 || c->dp_loopback || dp_phases_at_world1()));
     pf_touch(c);
     refuse_feedback(c);
     mb_flush(c);
@@ -2799,6 +2979,7 @@ int sacmi_dp_set_sharded(sacmi_ctx* c, int32_t on) {
     pf_touch(c);
     REQUIRE(c->comm || c->dp_loopback, SACMI_ESTATE, "sacmi_allreduce_init has not been called");
     REQUIRE(!on || c->dp_world <= kMaxShardWorld, SACMI_EVALUE, "sharded step: world > 64");
+    refuse_clip_sharded(c, on != 0);
     // leaving the sharded form: the moments whole on every rank first (the all-reduce form
     // steps every element from this rank's M, V) — a collective, like the switch itself
     if (!on) dp_gather_moments(c);

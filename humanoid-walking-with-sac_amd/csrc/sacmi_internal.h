@@ -108,6 +108,7 @@ inline int64_t round_up64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 // Null pointer (every production graph): no instruction beyond the test.
 typedef unsigned long long tl_word;
 enum TlKind : int {
+  TL_GRAD_SUMSQ = 0,   // (clip.hip; 0: the numbered kinds below keep their values and their end)
   TL_GEMM = 1, TL_FWD_X6, TL_FWD16, TL_AXK16, TL_AXK_X6, TL_DW_PART16, TL_DW_FIN, TL_HEADS,
   TL_SAMPLE_BWD, TL_MT_SAMPLE, TL_GATHER, TL_PER_F1, TL_PER_F2, TL_PER_F2B, TL_PER_F3,
   TL_PER_F4, TL_PER_UNFUSED, TL_ADAM, TL_SAMPLE_TAIL, TL_FWD16P, TL_DW_PART_X6,
@@ -528,6 +529,30 @@ bool gemm_level_pa_capable(const GemmBatch& b);
 
 
 constexpr int kMaxAdamSegs = 8;
+// Global-norm gradient clipping (clip.hip): three groups as the reference's three network
+// optimizers (q1, q2, policy); device state next to DevScalars, one per context.
+constexpr int kClipMaxGroups = 2;      // groups one launch covers (the critic range: q1, q2)
+constexpr int kClipThreads = 256;
+constexpr int kClipWgFloats = 16384;   // padded floats of a group per k_grad_sumsq workgroup
+constexpr int kClipMaxWgs = 64;        //   ... up to this many workgroups per group
+constexpr int kGnormRingSlots = 4096;
+struct ClipState {
+  float max_norm[3];   // q1, q2, policy (+inf: measured only)
+  float pad0;
+  float parked[4];     // the critic launch's norm q1, q2 and coef q1, q2 of this update
+  int64_t count;       // rows appended since creation
+  float fin[3][2];     // (-DSACMI_CLIP_SEPARATE_FINISH builds only: a finish launch's norm, coef)
+};
+// coef = min(1, max_norm / (norm + 1e-6f)) in fp32, as torch.nn.utils.clip_grad_norm_ forms it
+// (clamp(max=1.0): a NaN quotient stays NaN — no special case for a non-finite norm)
+__device__ __forceinline__ float clip_coef(float norm, float max_norm) {
+  const float c = max_norm / (norm + 1e-6f);
+  return c > 1.0f ? 1.0f : c;
+}
+inline int clip_workgroups(int64_t padded_floats) {
+  const int64_t n = (padded_floats + kClipWgFloats - 1) / kClipWgFloats;
+  return (int)(n < 1 ? 1 : n > kClipMaxWgs ? kClipMaxWgs : n);
+}
 struct AdamSeg { int64_t off, n; int step_idx; };
 struct AdamArgs {
   float* p; const float* g; float* m; float* v;
@@ -550,9 +575,45 @@ struct AdamArgs {
   // data-parallel critic step: the error flags summed over the ranks (kDpFlagN), combined into
   // the error word before the skip test (null: the local word alone)
   const float* err_flags;
+  // global-norm gradient clipping (clip.hip; sacmi_set_grad_clip).  clip_part null: none of it,
+  // the step as it always was.  Else the prologue of every workgroup sums each group's fp64
+  // workgroup partials (k_grad_sumsq) in index order — the same bits everywhere —, forms
+  // norm = (float)sqrt(sum) and coef = min(1, max_norm / (norm + 1e-6f)) in fp32, and steps
+  // segment i from (g * grad_scale) * coef[seg_group[i]].  The scalar tail records: the critic
+  // launch (clip_group0 0: q1, q2) parks its norms and coefficients in ClipState, the actor
+  // launch (clip_group0 2: policy) appends the update's row to gnorm_ring
+  const double* clip_part;
+  int clip_ngroups;                    // groups of this launch (critic 2, actor 1)
+  int clip_wg_begin[kClipMaxGroups + 1];   // group k's partials: [clip_wg_begin[k], [k + 1])
+  int seg_group[kMaxAdamSegs];         // launch-local group of each segment
+  int clip_group0;
+  ClipState* clip;                     // thresholds, parked critic values, row counter
+  float* gnorm_ring;                   // [kGnormRingSlots][SACMI_GNORM_COUNT]
+  // the synchronous step's host-mapped words where this launch stands in for a fused level
+  // (AdamFuse::loss_host / done_word: the scalar tail stores the same words in the same order)
+  float* loss_host;
+  int* done_word;
   tl_word* tl;
 };
 void launch_adam(const AdamArgs& a, hipStream_t s);
+
+// One launch per range: workgroup w of group k reduces, over the rows of the group's segments,
+// sum (g * grad_scale)^2 of the columns < kdim into part[clip_wg_begin[k] + w] (fp64).
+struct ClipSeg { int64_t off; int rows, ld, kdim, group; };
+struct GradSumsqArgs {
+  const float* g;
+  float grad_scale;
+  int nseg; ClipSeg seg[kMaxAdamSegs];
+  int ngroups;
+  int wg_begin[kClipMaxGroups + 1];
+  double* part;
+  ClipState* clip;       // (the separate-finish build's finish launch: thresholds in, fin out)
+  int group0;
+  tl_word* tl;
+};
+void launch_grad_sumsq(const GradSumsqArgs& a, hipStream_t s);
+// the thresholds, stream-ordered (kernel arguments: nothing of the host's is read later)
+void launch_set_clip(ClipState* cs, float q1, float q2, float pi, hipStream_t s);
 
 // Sharded data-parallel optimizer step (sacmi.hip enqueue_dp, ZeRO-1): each range (critic,
 // actor) is cut into `world` chunks of a kShardAlign-float multiple; rank r reduce-scatters

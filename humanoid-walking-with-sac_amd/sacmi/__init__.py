@@ -6,9 +6,9 @@ Public surface mirrors the reference (FilippoCrc/Humanoid-walking-with-SAC):
 """
 from .core import Config, Context, setsize  # noqa: F401
 from . import _lib  # noqa: F401
-from ._lib import STAT_NAMES  # noqa: F401
+from ._lib import GNORM_NAMES, STAT_NAMES  # noqa: F401
 
-__all__ = ["Config", "Context", "setsize", "STAT_NAMES"]
+__all__ = ["Config", "Context", "setsize", "STAT_NAMES", "GNORM_NAMES"]
 
 from .agent import SAC  # noqa: E402,F401
 from .networks import GaussianPolicy, QNetwork  # noqa: E402,F401

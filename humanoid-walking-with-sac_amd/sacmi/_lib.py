@@ -94,6 +94,9 @@ _PROTOS = {
     "sacmi_set_stats": [c_vp, ctypes.c_int32],
     "sacmi_stats": [c_vp, c_i32p],
     "sacmi_fetch_stats": [c_vp, c_f32p, ctypes.c_int32, c_i32p, c_i64p],
+    "sacmi_set_grad_clip": [c_vp, ctypes.c_double, ctypes.c_double],
+    "sacmi_grad_clip": [c_vp, c_f64p, c_f64p],
+    "sacmi_fetch_grad_norms": [c_vp, c_f32p, ctypes.c_int32, c_i32p, c_i64p],
     "sacmi_step_phase": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_float],
     "sacmi_grad_buffer": [c_vp, ctypes.c_int, ctypes.POINTER(c_vp), c_i64p],
     "sacmi_grad_arena_numel": [c_vp, c_i64p],
@@ -130,11 +133,15 @@ TL_KINDS = {1: "k_gemm", 2: "k_fwd_x6", 3: "k_fwd16", 4: "k_axk16", 5: "k_axk_x6
             7: "k_dw_fin", 8: "k_heads_sample", 9: "k_gemm_sample_bwd", 10: "k_mt_sample",
             11: "k_gather", 12: "k_per_f1", 13: "k_per_f2", 14: "k_per_f2b", 15: "k_per_f3",
             16: "k_per_f4", 17: "per_unfused", 18: "k_adam", 19: "k_sample_bwd_tail",
-            20: "k_fwd16p", 21: "k_dw_part_x6", 22: "k_per_feedback", 23: "k_update_stats"}
+            20: "k_fwd16p", 21: "k_dw_part_x6", 22: "k_per_feedback", 23: "k_update_stats",
+            0: "k_grad_sumsq"}
 # the columns of a diagnostics row, in id order (enum sacmi_stat, include/sacmi.h)
 STAT_NAMES = ("q1_mean", "q2_mean", "q_target_mean", "td_mean", "td_max", "q_pi_mean", "entropy",
               "alpha", "log_alpha", "alpha_loss", "reward_mean", "batch")
 STAT_COUNT = len(STAT_NAMES)
+# the columns of a gradient-norm row, in id order (enum sacmi_gnorm, include/sacmi.h)
+GNORM_NAMES = ("norm_q1", "norm_q2", "norm_pi", "coef_q1", "coef_q2", "coef_pi")
+GNORM_COUNT = len(GNORM_NAMES)
 EXPORTS = tuple(_PROTOS) + ("sacmi_abi_version", "sacmi_last_error")
 
 _lib = None

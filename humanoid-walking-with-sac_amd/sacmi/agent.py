@@ -131,8 +131,14 @@ class SAC:
                  networks: str = "model1", compute_dtype: str = "fp32",
                  prioritized_replay: bool = False, per_alpha: float = 0.6,
                  per_beta_start: float = 0.4, per_beta_frames: int = 100000,
-                 diagnostics: bool = False):
-        """``diagnostics``: every update also leaves one row of training diagnostics on the
+                 diagnostics: bool = False, max_grad_norm=None):
+        """``max_grad_norm``: global-norm gradient clipping, ``torch.nn.utils.clip_grad_norm_``
+        between ``backward()`` and each network optimizer's ``step()`` (q1, q2, policy; never
+        ``log_alpha``), computed on the device: a float for all three, or a
+        ``(critic, actor)`` pair; ``math.inf`` measures only.  Every update then leaves its
+        three pre-clip gradient norms and coefficients on the device (``sacmi.GNORM_NAMES``),
+        read with ``fetch_grad_norms()``.  A hyperparameter: not written to checkpoints.
+        ``diagnostics``: every update also leaves one row of training diagnostics on the
         device (``sacmi.STAT_NAMES``: mean Q values, TD error, entropy, alpha, ...), read with
         ``fetch_diagnostics()``; what ``update_parameters*`` return does not change.
         ``prioritized_replay``: the agent owns a prioritized buffer
@@ -197,6 +203,11 @@ class SAC:
                                               sync_python_random=sync_python_random)
         if diagnostics:
             self._ctx.set_stats(True)
+        if max_grad_norm is not None:
+            mc, ma = max_grad_norm if isinstance(max_grad_norm, (tuple, list)) else (max_grad_norm,) * 2
+            if not (float(mc) > 0 and float(ma) > 0):
+                raise ValueError("max_grad_norm must be positive (math.inf: measure only)")
+            self._ctx.set_grad_clip(float(mc), float(ma))
         st = random.getstate()             # device sampling stream starts at `random`'s
         self._ctx.set_mt(0, np.array(st[1][:624], np.uint32), st[1][624])
         self._mt_adopted = st[1]           # (the Python stream state the device holds)
@@ -319,6 +330,12 @@ class SAC:
         rows = self._ctx.fetch_losses(max_steps)
         return [{"q1_loss": float(r[0]), "q2_loss": float(r[1]), "policy_loss": float(r[2])}
                 for r in rows]
+
+    def fetch_grad_norms(self, max_rows=4096):
+        """The most recent updates' gradient-norm rows, oldest first, as dicts keyed by
+        ``sacmi.GNORM_NAMES`` ([] unless the agent was built with ``max_grad_norm``)."""
+        rows, _ = self._ctx.fetch_grad_norms(max_rows)
+        return [{k: float(v) for k, v in zip(L.GNORM_NAMES, r)} for r in rows]
 
     def fetch_diagnostics(self, max_rows=4096):
         """The most recent updates' diagnostics rows, oldest first, as dicts keyed by

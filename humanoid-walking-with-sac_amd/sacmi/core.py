@@ -271,6 +271,30 @@ class Context:
                ctypes.byref(n), ctypes.byref(total))
         return out[:n.value], int(total.value)
 
+    def set_grad_clip(self, max_norm_critic: float = 0.0, max_norm_actor: float = 0.0) -> None:
+        """Global-norm gradient clipping (sacmi.h sacmi_set_grad_clip): torch's
+        ``clip_grad_norm_`` for q1, q2 (``max_norm_critic`` each) and the policy
+        (``max_norm_actor``), computed on the device.  0, 0: off; ``math.inf`` (or 0 beside a
+        positive value): that range is measured only."""
+        L.call("sacmi_set_grad_clip", self._h, float(max_norm_critic), float(max_norm_actor))
+
+    def grad_clip(self):
+        """(max_norm_critic, max_norm_actor) in effect; (0.0, 0.0) while off."""
+        mc, ma = ctypes.c_double(), ctypes.c_double()
+        L.call("sacmi_grad_clip", self._h, ctypes.byref(mc), ctypes.byref(ma))
+        return float(mc.value), float(ma.value)
+
+    def fetch_grad_norms(self, max_rows: int = 4096):
+        """(rows float32 [n, 6], total): per update ``L.GNORM_NAMES`` — the pre-clip gradient
+        norms of q1, q2 and the policy and the coefficients applied — the most recent
+        min(total, 4096, max_rows) rows, oldest first.  Synchronises; reports no error."""
+        out = np.zeros((max(int(max_rows), 0), L.GNORM_COUNT), np.float32)
+        n = ctypes.c_int32()
+        total = ctypes.c_int64()
+        L.call("sacmi_fetch_grad_norms", self._h, L.fptr(out) if out.size else None, out.shape[0],
+               ctypes.byref(n), ctypes.byref(total))
+        return out[:n.value], int(total.value)
+
     def step_phase(self, batch: int, phase: int, grad_scale: float = 1.0, parity: int = 0,
                    have_batch: bool = False, ride_next: bool = False) -> None:
         if parity or have_batch or ride_next:

@@ -253,6 +253,51 @@ int sacmi_stats(sacmi_ctx* ctx, int32_t* on);
  * Read-only: reports and clears no error (sacmi_fetch_losses does that). */
 int sacmi_fetch_stats(sacmi_ctx* ctx, float* out, int32_t max_rows, int32_t* n_out, int64_t* total);
 
+/* ---- global-norm gradient clipping and per-update gradient norms ---------------------- */
+/* torch.nn.utils.clip_grad_norm_ between backward() and optimizer.step(), for the reference's
+ * three network optimizers (q1, q2, policy: sac_imp.py:101-125; log_alpha's own optimizer is
+ * never clipped).  Per update and group n, over the REAL elements of the group's gradient
+ * (torch's weight and bias elements: the storage's pad columns never count):
+ *     sumsq_n = sum (g * grad_scale)^2                        fp64, fixed order, no atomics
+ *     norm_n  = (float)sqrt(sumsq_n)
+ *     coef_n  = min(1.0f, max_norm_n / (norm_n + 1e-6f))      fp32
+ *     Adam steps the group from (g * grad_scale) * coef_n
+ * grad_scale is 1 on one GPU and 1/world in the data-parallel all-reduce form, where the
+ * reduction runs behind the collective: the norm is that of the mean gradient, the same on
+ * every rank.  The sharded data-parallel form would need one more collective and is refused:
+ * with clipping on, sacmi_step_dp on a sharded context, sacmi_dp_set_sharded(1) and a
+ * communicator initialised under $SACMI_DP_SHARD return SACMI_ESTATE before touching state.
+ *
+ * 0, 0 = off (default; the update's launches are exactly those of a context that never called
+ * this).  A positive value or +inf switches the feature on; with one of the two at 0 that
+ * range is measured only (as +inf).  Negative or NaN: SACMI_EVALUE.  critic applies to q1
+ * and to q2 separately.  With max_norm = +inf the coefficient is exactly 1 and the update's
+ * parameters and moments are bit-identical to an unclipped one.  The thresholds live on the
+ * device and are written stream-ordered: changing them re-captures nothing (switching the
+ * feature on or off selects another captured graph).  On, the fused update takes its Adam
+ * steps in launches of their own behind the weight-gradient levels (same arithmetic, same
+ * bits as the fused epilogues); everything else of the update is unchanged.
+ *
+ * A non-finite norm gets no special case (torch's error_if_nonfinite=False): the coefficient
+ * and then the group's parameters go non-finite, and the next update's policy sample reports
+ * SACMI_ENAN.
+ *
+ * SACMI_SLOT_GRAD holds the raw, pre-clip gradient (torch scales .grad in place; here the
+ * coefficient is applied inside the Adam step): multiply by the update's SACMI_GCOEF_* for
+ * torch's post-clip .grad.
+ *
+ * Every update that returns losses appends one row {norm q1, q2, pi, coef q1, q2, pi} (fp32) to
+ * a device ring of 4096 rows; a voided update (any SACMI_ENAN, the actor-batch one whose critic
+ * step stood included) appends none.  SACMI_GRAD_CLIP=<critic>[,<actor>] in the environment at
+ * sacmi_create switches it on from the start (one value: both ranges; "inf" accepted).
+ * Additive: the ABI version is unchanged. */
+int sacmi_set_grad_clip(sacmi_ctx* ctx, double max_norm_critic, double max_norm_actor);
+int sacmi_grad_clip(sacmi_ctx* ctx, double* max_norm_critic, double* max_norm_actor);
+enum sacmi_gnorm { SACMI_GNORM_Q1 = 0, SACMI_GNORM_Q2 = 1, SACMI_GNORM_PI = 2, SACMI_GCOEF_Q1 = 3,
+                   SACMI_GCOEF_Q2 = 4, SACMI_GCOEF_PI = 5, SACMI_GNORM_COUNT = 6 };
+/* as sacmi_fetch_stats: synchronises, most recent min(total, 4096, max_rows) rows oldest first */
+int sacmi_fetch_grad_norms(sacmi_ctx* ctx, float* out, int32_t max_rows, int32_t* n_out, int64_t* total);
+
 /* Data-parallel split of the step (one process per GPU).  phase 0: sample, gather,
  * forward, critic backward -> critic gradient buffer; phase 1: critic Adam + Polyak,
  * actor forward/backward -> actor gradient buffer; phase 2: actor Adam + alpha;
