@@ -3994,13 +3994,9 @@ void launch_alpha_sync(DevScalars* sc, const float* log_alpha, int err_skip, hip
 // ---------------------------------------------------------------------------
 // replay gather: deque positions -> ring slots -> critic input [s|1|a] and the
 // stacked policy input [s2|1|.. ; s|1|..]  (replay_buffer.py:15-19 + sac_imp.py:81-85)
-__global__ __launch_bounds__(128) void k_gather(GatherArgs a) {
-  const TlMark tl_mark(a.tl, TL_GATHER);
-  gather_row(a, blockIdx.x, threadIdx.x, 128);
-}
-
+// (k_gather: replay_dev.h, shared with the normalising form in obsnorm.hip)
 void launch_gather(const GatherArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_gather, dim3(a.B), dim3(128), 0, s, a);
+  hipLaunchKernelGGL(k_gather<false>, dim3(a.B), dim3(128), 0, s, a);
   HIP_LAUNCH_CHECK();
 }
 

@@ -226,29 +226,54 @@ __device__ __forceinline__ void mt_sample_body(const MtSampleArgs& a, int tbl_lo
 }
 
 
+// the state's float4 group q of a row (v: s, w: s2) normalised in place (NORM gathers)
+__device__ __forceinline__ void obs_normalize4(float4& v, float4& w, const ObsNormArgs& on, int q,
+                                               float clip) {
+  const float4 mu = reinterpret_cast<const float4*>(on.nmean)[q];
+  const float4 rs = reinterpret_cast<const float4*>(on.nrstd)[q];
+  v.x = obs_normalize(v.x, mu.x, rs.x, clip); v.y = obs_normalize(v.y, mu.y, rs.y, clip);
+  v.z = obs_normalize(v.z, mu.z, rs.z, clip); v.w = obs_normalize(v.w, mu.w, rs.w, clip);
+  w.x = obs_normalize(w.x, mu.x, rs.x, clip); w.y = obs_normalize(w.y, mu.y, rs.y, clip);
+  w.z = obs_normalize(w.z, mu.z, rs.z, clip); w.w = obs_normalize(w.w, mu.w, rs.w, clip);
+}
+
 // One replay row b into the minibatch buffers (replay_buffer.py:13-19 stacking):
 // xq[b] = [s | 1 | a], x2[b] = [s2 | 1 | .], x2[B+b] = [s | 1 | .], r[b], d[b].
 // Lanes lane, lane+nl, ... of the caller share the row.  x16 (act16 updates): the rows
 // are bf16 (rounded once here: every consumer rounds its operands to bf16 anyway).  The
 // ones column is written with the row (the two layouts share the buffers).
-__device__ __forceinline__ void gather_row16(const GatherArgs& a, int64_t slot, int b, int lane, int nl) {
+// NORM (sacmi_set_obs_norm, the update's own gather only — never a ride): s and s2 pass through
+// obs_normalize with the context's current vectors, before the one rounding to bf16; the ones
+// column, the actions, r and d are as stored.
+template <bool NORM = false>
+__device__ __forceinline__ void gather_row16(const GatherArgs& a, int64_t slot, int b, int lane, int nl,
+                                             const ObsNormArgs& on = ObsNormArgs{}) {
   const float* so = a.obs + slot * a.ldo;
   const float* s2 = a.obs2 + slot * a.ldo;
   const float* ac = a.act + slot * a.lda_;
   const uint32_t oq = (uint32_t)((size_t)b * a.ldx) * 2u, ot = oq;
   const uint32_t oa = (uint32_t)((size_t)(a.B + b) * a.ldx) * 2u;
   const int s4 = a.S >> 2;
+  float clip = 0.f;
+  if constexpr (NORM) clip = *on.clip;
   for (int q = lane; q < s4; q += nl) {
-    const float4 v = reinterpret_cast<const float4*>(so)[q];
-    const float4 w = reinterpret_cast<const float4*>(s2)[q];
+    float4 v = reinterpret_cast<const float4*>(so)[q];
+    float4 w = reinterpret_cast<const float4*>(s2)[q];
+    if constexpr (NORM) { obs_normalize4(v, w, on, q, clip); }
     const uint32_t vl = f2bf2(v.x, v.y), vh = f2bf2(v.z, v.w);
     st_wt8(a.xq, oq + 8u * q, vl, vh);
     st_wt8(a.x2, oa + 8u * q, vl, vh);
     st_wt8(a.x2, ot + 8u * q, f2bf2(w.x, w.y), f2bf2(w.z, w.w));
   }
   for (int q = 4 * s4 + lane; q < a.S; q += nl) {
-    const unsigned short v = f2bf(so[q]);
-    st_wt2(a.xq, oq + 2u * q, v); st_wt2(a.x2, oa + 2u * q, v); st_wt2(a.x2, ot + 2u * q, f2bf(s2[q]));
+    if constexpr (NORM) {
+      const unsigned short v = f2bf(obs_normalize(so[q], on.nmean[q], on.nrstd[q], clip));
+      const unsigned short w = f2bf(obs_normalize(s2[q], on.nmean[q], on.nrstd[q], clip));
+      st_wt2(a.xq, oq + 2u * q, v); st_wt2(a.x2, oa + 2u * q, v); st_wt2(a.x2, ot + 2u * q, w);
+    } else {
+      const unsigned short v = f2bf(so[q]);
+      st_wt2(a.xq, oq + 2u * q, v); st_wt2(a.x2, oa + 2u * q, v); st_wt2(a.x2, ot + 2u * q, f2bf(s2[q]));
+    }
   }
   for (int j = lane; j < a.A; j += nl) st_wt2(a.xq, oq + 2u * (a.S + 1 + j), f2bf(ac[j]));
   if (lane == 0) {
@@ -259,10 +284,12 @@ __device__ __forceinline__ void gather_row16(const GatherArgs& a, int64_t slot, 
   }
 }
 
-__device__ __forceinline__ void gather_row(const GatherArgs& a, int b, int lane, int nl) {
+template <bool NORM = false>
+__device__ __forceinline__ void gather_row(const GatherArgs& a, int b, int lane, int nl,
+                                           const ObsNormArgs& on = ObsNormArgs{}) {
   const int64_t slot = a.by_slot ? (int64_t)a.idx[b] : (a.sc->head + (int64_t)a.idx[b]) % a.capacity;
   if (a.x16) {
-    gather_row16(a, slot, b, lane, nl);
+    gather_row16<NORM>(a, slot, b, lane, nl, on);
     return;
   }
   const float* so = a.obs + slot * a.ldo;
@@ -277,16 +304,25 @@ __device__ __forceinline__ void gather_row(const GatherArgs& a, int b, int lane,
   const uint32_t oq = (uint32_t)((size_t)b * a.ldx) * 4u, ot = oq;
   const uint32_t oa = (uint32_t)((size_t)(a.B + b) * a.ldx) * 4u;
   const int s4 = a.S >> 2;
+  float clip = 0.f;
+  if constexpr (NORM) clip = *on.clip;
   for (int q = lane; q < s4; q += nl) {
-    const float4 v = reinterpret_cast<const float4*>(so)[q];
-    const float4 w = reinterpret_cast<const float4*>(s2)[q];
+    float4 v = reinterpret_cast<const float4*>(so)[q];
+    float4 w = reinterpret_cast<const float4*>(s2)[q];
+    if constexpr (NORM) { obs_normalize4(v, w, on, q, clip); }
     st_wt4(a.xq, oq + 16u * q, v);
     st_wt4(a.x2, oa + 16u * q, v);
     st_wt4(a.x2, ot + 16u * q, w);
   }
   for (int q = 4 * s4 + lane; q < a.S; q += nl) {
-    const float v = so[q];
-    st_wt(xq + q, v); st_wt(xa + q, v); st_wt(xt + q, s2[q]);
+    if constexpr (NORM) {
+      const float v = obs_normalize(so[q], on.nmean[q], on.nrstd[q], clip);
+      const float w = obs_normalize(s2[q], on.nmean[q], on.nrstd[q], clip);
+      st_wt(xq + q, v); st_wt(xa + q, v); st_wt(xt + q, w);
+    } else {
+      const float v = so[q];
+      st_wt(xq + q, v); st_wt(xa + q, v); st_wt(xt + q, s2[q]);
+    }
   }
   for (int j = lane; j < a.A; j += nl) st_wt(xq + a.S + 1 + j, ac[j]);
   if (lane == 0) {
@@ -294,6 +330,14 @@ __device__ __forceinline__ void gather_row(const GatherArgs& a, int b, int lane,
     st_wt(a.r + b, a.rew[slot]);
     st_wt(a.d + b, a.done[slot]);
   }
+}
+
+// The update's own gather launch: a workgroup per row.  k_gather<false> (kernels.hip) takes
+// GatherArgs alone; k_gather<true, ObsNormArgs> (obsnorm.hip) a second kernel parameter
+template <bool NORM, class... On>
+__global__ __launch_bounds__(128) void k_gather(GatherArgs a, On... on) {
+  const TlMark tl_mark(a.tl, TL_GATHER);
+  gather_row<NORM>(a, blockIdx.x, threadIdx.x, 128, on...);
 }
 
 // Rows b0 + i * bstep (i < R) by one wave, every load of the R rows issued before any

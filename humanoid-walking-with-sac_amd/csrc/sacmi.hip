@@ -289,6 +289,14 @@ struct sacmi_ctx {
   int clip_wgs[3] = {};
   bool clip_on = false;
   double clip_max[2] = {};             // effective thresholds (critic, actor) while on
+  // sacmi_set_obs_norm (obsnorm.hip): the running moments on_mom [3][Sp] fp64 (count, mean, M2
+  // per column), the vectors the consumers read on_vec (nmean [Sp] | nrstd [Sp] | clip) and the
+  // one-state select_action's normalised fc1 operand on_actx [Kx] (the GEMV path must not write
+  // a drawn-ahead x2); allocated when first needed.  on_mode: 0 off, 1 on, 2 on and frozen
+  sacmi::DevBuf<double> on_mom;
+  sacmi::DevBuf<float> on_vec, on_actx;
+  int on_mode = 0;
+  double on_eps = 1e-8, on_clip = 10.0;
   std::map<sacmi::GraphKey, hipGraphExec_t> graphs;
   bool use_graphs = true;
   bool G_external = false;
@@ -873,9 +881,18 @@ static GatherArgs gather_args(sacmi_ctx* c, int B, const BatchBufs& bb, bool per
   return g;
 }
 
+// Observation normalisation on: the gather takes ObsNormArgs as a kernel parameter of its own
+// (GatherArgs / RideAlong / GemmBatch keep their bytes), so no gather rides in a GEMM launch
+// and nothing is drawn ahead: every update runs its own sampler + gather launches
+static bool obs_norm_on(const sacmi_ctx* c) { return c->on_mode != 0; }
+static ObsNormArgs obs_norm_args(const sacmi_ctx* c) {
+  const int Sp = round_up(c->S, 4);
+  return ObsNormArgs{c->on_vec.p, c->on_vec.p + Sp, c->on_vec.p + 2 * Sp};
+}
+
 // Can the next update's sampling + gather ride along in this update's launches?
 static bool ride_possible(sacmi_ctx* c, int B) {
-  return c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
+  return !obs_norm_on(c) && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
          mt_sample_lds_words(mt_sample_tbl_log2(B), sample_setsize(B)) * 4 <= kRideLdsBytes;
 }
 
@@ -885,7 +902,7 @@ static bool ride_possible(sacmi_ctx* c, int B) {
 // slots; a row a wave, every load before any store).  (The gather in L10 measured no
 // overlap: k_gemm_sample_bwd's 1024-thread workgroups fit one per CU)
 static bool ride_b_possible(sacmi_ctx* c, int B) {
-  return c->cfg.replay_kind == SACMI_REPLAY_UNIFORM && c->bf16 && B >= 2048 &&
+  return !obs_norm_on(c) && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM && c->bf16 && B >= 2048 &&
          mt_sample_lds_words(mt_sample_tbl_log2(B, true), sample_setsize(B)) * 4 <=
              (size_t)kDw16LdsBytes;
 }
@@ -915,7 +932,8 @@ static void enqueue_sample_gather(sacmi_ctx* c, int B, int parity, bool dev_idx,
   if (mark(c, ("gather" + t).c_str())) {
     GatherArgs ga = gather_args(c, B, bb, per);
     ga.tl = c->tl_cur;
-    launch_gather(ga, s);
+    if (obs_norm_on(c)) launch_gather_norm(ga, obs_norm_args(c), s);
+    else launch_gather(ga, s);
   }
 }
 
@@ -1124,6 +1142,8 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
   // every Adam step of this update but the sharded data-parallel form's own (enqueue_dp_sharded
   // steps this rank's chunks) reads and writes the whole of M, V
   if ((phase_mask & 6) && !c->dp_sharding_now) require_moments_whole(c);
+  REQUIRE(!(obs_norm_on(c) && ride_next), SACMI_ESTATE,
+          "observation normalisation is on: no gather rides along or is drawn ahead");
   c->site_counter = 0;
   const BatchBufs bb = batch_bufs(c, parity);
   // where the next update's sampling + gather ride: L12 / L13 (placement A, batch <= ~2k,
@@ -1637,7 +1657,7 @@ static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_
                phase_mask | (grad_scale != 1.f ? 8 : 0) | (c->keep_grads ? 16 : 0) |
                    (pr.parity ? 32 : 0) | (pr.have_batch ? 64 : 0) | (pr.ride_next ? 128 : 0) |
                    (c->mb_graph ? 256 : 0) | (c->per_feedback ? 512 : 0) |
-                   (c->stats_on ? 1024 : 0) | (c->clip_on ? 2048 : 0),
+                   (c->stats_on ? 1024 : 0) | (c->clip_on ? 2048 : 0) | (obs_norm_on(c) ? 4096 : 0),
                use_ring ? c->ring_slots : 0,
                per_graph_len(c), reps};
   auto it = c->graphs.find(key);
@@ -2027,6 +2047,7 @@ int sacmi_device_count(int* n) {
 }
 
 static void set_grad_clip(sacmi_ctx* c, double mc, double ma);
+static void set_obs_norm(sacmi_ctx* c, int32_t mode, double eps, double clip);
 
 int sacmi_create(const sacmi_config* cfg, int device, sacmi_ctx** out) {
   return guard([&] {
@@ -2095,6 +2116,12 @@ int sacmi_create(const sacmi_config* cfg, int device, sacmi_ctx** out) {
       set_grad_clip(c.get(), mc, ma);
       CHECK_HIP(hipStreamSynchronize(c->stream));
     }
+    // SACMI_OBS_NORM=1: observation normalisation on from creation (sacmi_set_obs_norm mode 1,
+    // eps 1e-8, clip 10)
+    if (const char* on = getenv("SACMI_OBS_NORM"); on && on[0] == '1') {
+      set_obs_norm(c.get(), 1, 1e-8, 10.0);
+      CHECK_HIP(hipStreamSynchronize(c->stream));
+    }
     *out = c.release();
   });
 }
@@ -2132,6 +2159,7 @@ int sacmi_destroy(sacmi_ctx* c) {
     c->per_u.release(); c->per_uin.release(); c->per_owner.release(); c->per_bad.release();
     c->stats_ring.release(); c->stats_cnt.release(); c->stats_ws.release();
     c->clip_state.release(); c->clip_part.release(); c->gnorm_ring.release();
+    c->on_mom.release(); c->on_vec.release(); c->on_actx.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);
@@ -2341,6 +2369,21 @@ static MailboxArgs mailbox_args(sacmi_ctx* c) {
 }
 }  // namespace sacmi
 
+static void obs_norm_alloc(sacmi_ctx* c) {
+  if (c->on_mom.p) return;
+  const int Sp = sacmi::round_up(c->S, 4);
+  c->on_mom.alloc((size_t)3 * Sp);
+  c->on_vec.alloc((size_t)2 * Sp + 4);
+  c->on_actx.alloc((size_t)c->Kx);
+  sacmi::launch_obs_refresh(c->on_mom.p, c->on_vec.p, c->S, Sp, c->on_eps, (float)c->on_clip, c->stream);
+}
+static void obs_stats_chunk(sacmi_ctx* c, const float* rows, int m) {
+  sacmi::ObsStatsArgs oa{};
+  oa.s = rows; oa.m = m; oa.S = c->S; oa.Sp = sacmi::round_up(c->S, 4);
+  oa.mom = c->on_mom.p; oa.vec = c->on_vec.p; oa.eps = c->on_eps;
+  sacmi::launch_obs_stats(oa, c->stream);
+}
+
 // Rows [n] of transitions into the ring (deque(maxlen) semantics), from either layout:
 // separate arrays (packed == nullptr) or packed rows [n][2S + A + 2] = s | a | r | s2 | d.
 static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float* r, const float* s2,
@@ -2353,7 +2396,10 @@ static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float*
     // update's sampler (uniform replay; every other path flushes them first)
     const int S = c->S, A = c->A;
     const int64_t rowf = 2 * S + A + 2;
-    if (c->mb_host && !c->inflight && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
+    // (observation statistics updating, mode 1: every row takes the chunked path below, where
+    // k_obs_stats sees it; rows already pending are flushed first, uncounted: they were pushed
+    // before the mode was set)
+    if (c->mb_host && !c->inflight && c->on_mode != 1 && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
         c->mb_pending + n <= sacmi_ctx::kMbRows && c->mb_pending + n <= c->capacity) {
       // (rows pending beyond the capacity would map two rows onto one ring slot in the
       // sampler's scatter, stored in no fixed order: the chunked path's `skip` handles that)
@@ -2450,6 +2496,10 @@ static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float*
     pa.head = len < cap ? 0 : wpos;
     launch_push_rows(pa, c->stream);
     CHECK_HIP(hipGetLastError());
+    // the chunk's states into the running moments, from the same staging right behind the
+    // scatter: the slot's reuse waits for this stream (push_zc_epoch / the copy's event, and
+    // the next copy into `stage` is stream-ordered behind this reader)
+    if (c->on_mode == 1) obs_stats_chunk(c, pa.stage, (int)m);
   }
   const int64_t added = n - skip;
   if (c->cfg.replay_kind == SACMI_REPLAY_PER) {
@@ -2870,8 +2920,115 @@ int sacmi_fetch_grad_norms(sacmi_ctx* c, float* out, int32_t max_rows, int32_t* 
   });
 }
 
+// ---------------------------------------------------------------------------
+// running observation normalisation (obsnorm.hip)
+static void refuse_obs_norm(const sacmi_ctx* c) {
+  REQUIRE(!(c && obs_norm_on(c)), SACMI_ESTATE,
+          "observation normalisation is on: no phase-split or data-parallel update (each rank's "
+          "shard would grow statistics of its own; a collective over the moments is not built)");
+}
+
+static void set_obs_norm(sacmi_ctx* c, int32_t mode, double eps, double clip) {
+  REQUIRE(c, SACMI_EVALUE, "null ctx");
+  REQUIRE(mode >= 0 && mode <= 2, SACMI_EVALUE, "mode must be 0 (off), 1 (on) or 2 (on, frozen)");
+  REQUIRE(std::isfinite(eps) && eps >= 0.0, SACMI_EVALUE, "eps must be finite and >= 0");
+  REQUIRE(clip > 0.0, SACMI_EVALUE, "clip must be > 0 or +inf");   // (false for a NaN)
+  pf_touch(c);
+  mb_flush(c);      // (rows pushed under the old mode reach the ring under it)
+  c->on_eps = eps;
+  c->on_clip = clip;
+  c->on_mode = mode;   // (on / off is part of the graph key; 1 <-> 2 is host state only)
+  if (mode == 0 && !c->on_mom.p) return;
+  obs_norm_alloc(c);
+  // stream-ordered: updates already enqueued keep the vectors they were enqueued under
+  launch_obs_refresh(c->on_mom.p, c->on_vec.p, c->S, round_up(c->S, 4), eps, (float)clip, c->stream);
+}
+
+int sacmi_set_obs_norm(sacmi_ctx* c, int32_t mode, double eps, double clip) {
+  return guard([&] { set_obs_norm(c, mode, eps, clip); });
+}
+
+int sacmi_obs_norm(sacmi_ctx* c, int32_t* mode, double* eps, double* clip) {
+  return guard([&] {
+    REQUIRE(c && mode && eps && clip, SACMI_EVALUE, "null argument");
+    *mode = c->on_mode;
+    *eps = c->on_eps;
+    *clip = c->on_clip;
+  });
+}
+
+int sacmi_obs_norm_update(sacmi_ctx* c, const float* states, int64_t n) {
+  return guard([&] {
+    REQUIRE(c && (states || n == 0), SACMI_EVALUE, "null argument");
+    REQUIRE(n >= 0, SACMI_EVALUE, "n < 0");
+    REQUIRE(obs_norm_on(c), SACMI_ESTATE, "observation normalisation is off");
+    pf_touch(c);
+    mb_flush(c);    // (rows pushed before this call reach the device before it)
+    // chunks through the push's device staging (stream-ordered behind its last reader); the
+    // wait: `states` may be pinned memory, which the copy reads when the stream reaches it
+    for (int64_t i = 0; i < n; i += kObsMaxRows) {
+      const int m = (int)std::min<int64_t>(kObsMaxRows, n - i);
+      CHECK_HIP(hipMemcpyAsync(c->stage.p, states + i * c->S, (size_t)m * c->S * 4, hipMemcpyHostToDevice,
+                               c->stream));
+      CHECK_HIP(hipStreamSynchronize(c->stream));
+      obs_stats_chunk(c, c->stage.p, m);
+    }
+  });
+}
+
+int sacmi_obs_norm_get_moments(sacmi_ctx* c, double* count, double* mean, double* m2, int32_t S) {
+  return guard([&] {
+    REQUIRE(c && count && mean && m2, SACMI_EVALUE, "null argument");
+    REQUIRE(S == c->S, SACMI_EVALUE, "S must be the context's state_dim");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    *count = 0.0;
+    std::fill(mean, mean + S, 0.0);
+    std::fill(m2, m2 + S, 0.0);
+    if (!c->on_mom.p) return;      // (never switched on: no rows counted)
+    const int Sp = round_up(S, 4);
+    CHECK_HIP(hipMemcpy(count, c->on_mom.p, 8, hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(mean, c->on_mom.p + Sp, (size_t)S * 8, hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(m2, c->on_mom.p + 2 * Sp, (size_t)S * 8, hipMemcpyDeviceToHost));
+  });
+}
+
+int sacmi_obs_norm_set_moments(sacmi_ctx* c, double count, const double* mean, const double* m2,
+                               int32_t S) {
+  return guard([&] {
+    REQUIRE(c && mean && m2, SACMI_EVALUE, "null argument");
+    REQUIRE(S == c->S, SACMI_EVALUE, "S must be the context's state_dim");
+    REQUIRE(std::isfinite(count) && count >= 0.0, SACMI_EVALUE, "count must be finite and >= 0");
+    for (int k = 0; k < S; ++k)
+      REQUIRE(std::isfinite(mean[k]) && std::isfinite(m2[k]) && m2[k] >= 0.0, SACMI_EVALUE,
+              "mean must be finite, m2 finite and >= 0");
+    pf_touch(c);
+    obs_norm_alloc(c);
+    const int Sp = round_up(S, 4);
+    std::vector<double> h((size_t)3 * Sp, 0.0);
+    for (int k = 0; k < S; ++k) { h[k] = count; h[Sp + k] = mean[k]; h[2 * Sp + k] = m2[k]; }
+    CHECK_HIP(hipMemcpyAsync(c->on_mom.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
+    launch_obs_refresh(c->on_mom.p, c->on_vec.p, S, Sp, c->on_eps, (float)c->on_clip, c->stream);
+    CHECK_HIP(hipStreamSynchronize(c->stream));   // (h leaves scope)
+  });
+}
+
+int sacmi_obs_norm_get_vectors(sacmi_ctx* c, float* nmean, float* nrstd, int32_t S) {
+  return guard([&] {
+    REQUIRE(c && nmean && nrstd, SACMI_EVALUE, "null argument");
+    REQUIRE(S == c->S, SACMI_EVALUE, "S must be the context's state_dim");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    std::fill(nmean, nmean + S, 0.f);
+    std::fill(nrstd, nrstd + S, 1.f);
+    if (!c->on_vec.p) return;      // (never switched on: the identity)
+    const int Sp = round_up(S, 4);
+    CHECK_HIP(hipMemcpy(nmean, c->on_vec.p, (size_t)S * 4, hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(nrstd, c->on_vec.p + Sp, (size_t)S * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 int sacmi_step_phase(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_scale) {
   return guard([&] {
+    refuse_obs_norm(c);
     pf_touch(c);
     refuse_feedback(c);
     REQUIRE(phase >= 0 && phase <= 3, SACMI_EVALUE, "phase must be 0, 1, 2 or 3");
@@ -2883,6 +3040,7 @@ int sacmi_step_phase(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_scal
 int sacmi_step_phase_ex(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_scale,
                         int32_t parity, int32_t have_batch, int32_t ride_next) {
   return guard([&] {
+    refuse_obs_norm(c);
     pf_touch(c);
     refuse_feedback(c);
     REQUIRE(phase >= 0 && phase <= 3, SACMI_EVALUE, "phase must be 0, 1, 2 or 3");
@@ -2945,6 +3103,7 @@ int sacmi_dp_loopback_init(sacmi_ctx* c, int32_t world) {
 
 int sacmi_step_dp(sacmi_ctx* c, int32_t batch, int32_t n_updates) {
   return guard([&] {
+    refuse_obs_norm(c);
     refuse_clip_sharded(c, c->dp_shard && (c->dp_world > 1 || c->dp_loopback || dp_phases_at_world1()));
     pf_touch(c);
     refuse_feedback(c);
@@ -3488,8 +3647,15 @@ int sacmi_act(sacmi_ctx* c, const float* states, int32_t n, int32_t deterministi
     // one state (the env-rate call): the policy forward as GEMVs (k_act_gemv / k_act_heads:
     // a wave per output instead of 32-row level tiles that use one row), fp32, from the
     // mapped staging, the action back into it, the host polling the heads' done word
+    // observation normalisation: one elementwise launch in front of fc1 writes the states,
+    // normalised, with the ones column: into on_actx for the one-state GEMVs, else into x2
+    // (from the mapped staging or in place), which fc1 then reads
+    const bool norm = obs_norm_on(c);
+    if (norm)
+      launch_obs_normalize(zc ? c->act_host_dev : c->x2.p, Kx, gemv ? c->on_actx.p : c->x2.p, Kx, n, S,
+                           obs_norm_args(c), s);
     if (gemv) {
-      const float* x = c->act_host_dev;
+      const float* x = norm ? c->on_actx.p : c->act_host_dev;
       int K = S + 1, ldw = c->p_fc[0].ld;
       const float* Wl = c->P.p + c->p_fc[0].off;
       for (int l = 0; l < c->nh; ++l) {
@@ -3526,7 +3692,7 @@ int sacmi_act(sacmi_ctx* c, const float* states, int32_t n, int32_t deterministi
     if (eps && !deterministic)
       CHECK_HIP(hipMemcpyAsync(c->eps.p, esrc, (size_t)n * A * 4, hipMemcpyHostToDevice, s));
     Level l1;
-    l1.add(gd(zc ? c->act_host_dev : c->x2.p, Kx, 1, c->P.p + c->p_fc[0].off, c->p_fc[0].ld, 1, c->hp[0].p, Hd,
+    l1.add(gd(zc && !norm ? c->act_host_dev : c->x2.p, Kx, 1, c->P.p + c->p_fc[0].off, c->p_fc[0].ld, 1, c->hp[0].p, Hd,
               n, H, S + 1, EPI_RELU));
     l1.b.bf16 = c->bf16;
     launch_gemm(l1.b, s);

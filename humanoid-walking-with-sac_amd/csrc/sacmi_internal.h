@@ -630,6 +630,48 @@ void launch_alpha_sync(DevScalars* sc, const float* log_alpha, int err_skip, hip
 
 void launch_gather(const GatherArgs& a, hipStream_t s);
 
+// Running observation normalisation (obsnorm.hip; sacmi_set_obs_norm).  Device state, one per
+// context, allocated when first switched on:
+//   mom [3][Sp] fp64: per column k the rows counted, the mean and M2 (the sum of squared
+//       deviations from the mean); Sp = S rounded up to 4.  The count is kept per column (all
+//       equal): every column's owner thread then reads and writes words of its own only
+//   vec [2][Sp] + 4 fp32: nmean | nrstd (pads: mean 0, rstd 1) | clip — what the consumers read
+// The consumers' view: a small argument block of its own — GatherArgs, RideAlong and GemmBatch
+// keep their bytes (the batch-256 levels are kernel-argument sensitive)
+struct ObsNormArgs {
+  const float* nmean;   // [Sp], 16-byte aligned
+  const float* nrstd;   // [Sp]
+  const float* clip;    // one float (+inf: no clipping); read on the device: changing it
+                        //   re-captures nothing
+};
+// y = clamp((x - nmean) * nrstd, -clip, clip) in fp32: two roundings and nothing to contract;
+// compares, not fminf / fmaxf: a NaN stays a NaN (the policy sample's validation reports it)
+__device__ __forceinline__ float obs_normalize(float x, float mu, float rs, float c) {
+  const float t = (x - mu) * rs;
+  return t < -c ? -c : (t > c ? c : t);
+}
+constexpr int kObsCols = 16;        // columns per k_obs_stats workgroup
+constexpr int kObsRowLanes = 16;    //   ... x row lanes: 256 threads
+constexpr int kObsMaxRows = 1024;   // rows per chunk (the push chunk)
+// One chunk s[m][S] (row-major, m <= kObsMaxRows; device or host-mapped memory) merged into
+// the running moments, and the vectors refreshed
+struct ObsStatsArgs {
+  const float* s;
+  int m, S, Sp;
+  double* mom;
+  float* vec;
+  double eps;
+};
+void launch_obs_stats(const ObsStatsArgs& a, hipStream_t s);
+// the vectors from the moments as they stand (new moments or eps), and the clip word
+void launch_obs_refresh(const double* mom, float* vec, int S, int Sp, double eps, float clip,
+                        hipStream_t s);
+// dst[i][k] = obs_normalize(src[i][k]) for k < S, 1 at S, 0 up to ldd (select_action's fc1
+// operand; in place when dst == src and the strides agree)
+void launch_obs_normalize(const float* src, int lds, float* dst, int ldd, int n, int S,
+                          const ObsNormArgs& on, hipStream_t s);
+void launch_gather_norm(const GatherArgs& a, const ObsNormArgs& on, hipStream_t s);
+
 // Rows sacmi_push left in host-mapped staging for the next synchronous update (the
 // trainer's row per env step): that update's sampler kernel scatters them into the ring
 // before it draws, instead of a scatter launch of their own ahead of the update

@@ -97,6 +97,12 @@ _PROTOS = {
     "sacmi_set_grad_clip": [c_vp, ctypes.c_double, ctypes.c_double],
     "sacmi_grad_clip": [c_vp, c_f64p, c_f64p],
     "sacmi_fetch_grad_norms": [c_vp, c_f32p, ctypes.c_int32, c_i32p, c_i64p],
+    "sacmi_set_obs_norm": [c_vp, ctypes.c_int32, ctypes.c_double, ctypes.c_double],
+    "sacmi_obs_norm": [c_vp, c_i32p, c_f64p, c_f64p],
+    "sacmi_obs_norm_update": [c_vp, c_f32p, ctypes.c_int64],
+    "sacmi_obs_norm_get_moments": [c_vp, c_f64p, c_f64p, c_f64p, ctypes.c_int32],
+    "sacmi_obs_norm_set_moments": [c_vp, ctypes.c_double, c_f64p, c_f64p, ctypes.c_int32],
+    "sacmi_obs_norm_get_vectors": [c_vp, c_f32p, c_f32p, ctypes.c_int32],
     "sacmi_step_phase": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_float],
     "sacmi_grad_buffer": [c_vp, ctypes.c_int, ctypes.POINTER(c_vp), c_i64p],
     "sacmi_grad_arena_numel": [c_vp, c_i64p],

@@ -131,8 +131,18 @@ class SAC:
                  networks: str = "model1", compute_dtype: str = "fp32",
                  prioritized_replay: bool = False, per_alpha: float = 0.6,
                  per_beta_start: float = 0.4, per_beta_frames: int = 100000,
-                 diagnostics: bool = False, max_grad_norm=None):
-        """``max_grad_norm``: global-norm gradient clipping, ``torch.nn.utils.clip_grad_norm_``
+                 diagnostics: bool = False, max_grad_norm=None,
+                 normalize_obs: bool = False, obs_clip: float = 10.0, obs_norm_eps: float = 1e-8):
+        """``normalize_obs``: running observation normalisation on the device.  The replay keeps
+        raw observations; every update's minibatch (state and next state) and every
+        ``select_action`` state pass through ``clamp((x - mean) / sqrt(var + obs_norm_eps),
+        -obs_clip, obs_clip)`` with the running mean and population variance of the states
+        pushed so far (counted when the rows reach the device: at the next update at the
+        latest).  ``obs_norm_state()`` / ``set_obs_norm_state()`` read and set the statistics,
+        ``freeze_obs_norm()`` stops pushes from updating them (evaluation, fine-tuning),
+        ``update_obs_norm(states)`` adds rows by hand (terminal observations); checkpoints
+        carry them.  ``obs_clip=math.inf``: no clipping.
+        ``max_grad_norm``: global-norm gradient clipping, ``torch.nn.utils.clip_grad_norm_``
         between ``backward()`` and each network optimizer's ``step()`` (q1, q2, policy; never
         ``log_alpha``), computed on the device: a float for all three, or a
         ``(critic, actor)`` pair; ``math.inf`` measures only.  Every update then leaves its
@@ -208,6 +218,8 @@ class SAC:
             if not (float(mc) > 0 and float(ma) > 0):
                 raise ValueError("max_grad_norm must be positive (math.inf: measure only)")
             self._ctx.set_grad_clip(float(mc), float(ma))
+        if normalize_obs:
+            self._ctx.set_obs_norm(1, float(obs_norm_eps), float(obs_clip))
         st = random.getstate()             # device sampling stream starts at `random`'s
         self._ctx.set_mt(0, np.array(st[1][:624], np.uint32), st[1][624])
         self._mt_adopted = st[1]           # (the Python stream state the device holds)
@@ -337,6 +349,59 @@ class SAC:
         rows, _ = self._ctx.fetch_grad_norms(max_rows)
         return [{k: float(v) for k, v in zip(L.GNORM_NAMES, r)} for r in rows]
 
+    # -- observation normalisation (SAC(normalize_obs=True)) ---------------------------------
+    def _obs_norm_mode(self):
+        return self._ctx.obs_norm()[0]
+
+    def obs_norm_state(self):
+        """``{"count", "mean", "var"}``: rows counted, running mean and population variance
+        (float64 [state_dim]) of the stored states; zeros before the first row."""
+        self._flush_device()
+        count, mean, m2 = self._ctx.obs_norm_moments()
+        return {"count": count, "mean": mean, "var": m2 / count if count > 0 else np.zeros_like(m2)}
+
+    def set_obs_norm_state(self, count, mean, var):
+        """Replace the running statistics (e.g. with those of another run)."""
+        self._flush_device()
+        var = np.asarray(var, np.float64)
+        self._ctx.set_obs_norm_moments(float(count), mean, var * float(count))
+
+    def freeze_obs_norm(self, flag=True):
+        """``True``: pushes stop updating the statistics (they keep normalising); ``False``:
+        they resume.  Needs ``normalize_obs=True``."""
+        mode, eps, clip = self._ctx.obs_norm()
+        if mode == 0:
+            raise RuntimeError("observation normalisation is off (SAC(normalize_obs=True))")
+        self._flush_device()       # (rows staged so far are counted under the mode they met)
+        self._ctx.set_obs_norm(2 if flag else 1, eps, clip)
+
+    def update_obs_norm(self, states):
+        """Count rows of states [n, state_dim] into the statistics, frozen or not."""
+        self._flush_device()
+        self._ctx.obs_norm_update(states)
+
+    def _obs_norm_entry(self):
+        """The checkpoint entry (None while the feature is off)."""
+        mode, eps, clip = self._ctx.obs_norm()
+        if mode == 0:
+            return None
+        self._flush_device()
+        count, mean, m2 = self._ctx.obs_norm_moments()
+        return {"count": torch.tensor(count, dtype=torch.float64), "mean": torch.from_numpy(mean),
+                "m2": torch.from_numpy(m2), "eps": float(eps), "clip": float(clip)}
+
+    def _load_obs_norm(self, ck):
+        """Restore a checkpoint's statistics, eps and clip (the mode stays, off -> on); a
+        checkpoint without the entry leaves everything as it is."""
+        e = ck.get("obs_norm")
+        if e is None:
+            return
+        self._flush_device()
+        mode = self._obs_norm_mode()
+        self._ctx.set_obs_norm(mode if mode else 1, float(e["eps"]), float(e["clip"]))
+        self._ctx.set_obs_norm_moments(float(e["count"]), np.asarray(e["mean"], np.float64),
+                                       np.asarray(e["m2"], np.float64))
+
     def fetch_diagnostics(self, max_rows=4096):
         """The most recent updates' diagnostics rows, oldest first, as dicts keyed by
         ``sacmi.STAT_NAMES`` ([] unless the agent was built with ``diagnostics=True``)."""
@@ -352,17 +417,22 @@ class SAC:
 
     # -- checkpoints (sac_imp.py:154-233) ----------------------------------------------------
     def save(self, path):
-        torch.save({"policy_state_dict": self.policy.state_dict(),
-                    "q1_state_dict": self.q1.state_dict(),
-                    "q2_state_dict": self.q2.state_dict(),
-                    "q1_target_state_dict": self.q1_target.state_dict(),
-                    "q2_target_state_dict": self.q2_target.state_dict(),
-                    "alpha": self.alpha}, path)
+        ck = {"policy_state_dict": self.policy.state_dict(),
+              "q1_state_dict": self.q1.state_dict(),
+              "q2_state_dict": self.q2.state_dict(),
+              "q1_target_state_dict": self.q1_target.state_dict(),
+              "q2_target_state_dict": self.q2_target.state_dict(),
+              "alpha": self.alpha}
+        on = self._obs_norm_entry()
+        if on is not None:
+            ck["obs_norm"] = on
+        torch.save(ck, path)
 
     def load(self, path):
         ck = _load_checkpoint_file(path)
         self._load_nets(ck)
         self.alpha = ck["alpha"]
+        self._load_obs_norm(ck)
 
     def _load_nets(self, ck):
         for name in ("policy", "q1", "q2", "q1_target", "q2_target"):
@@ -398,6 +468,9 @@ class SAC:
                                    "reward": torch.from_numpy(r),
                                    "next_state": torch.from_numpy(s2),
                                    "done": torch.from_numpy(d)}
+        on = self._obs_norm_entry()
+        if on is not None:
+            ck["obs_norm"] = on
         # NB: the reference only calls torch.save when replay_buffer=True (an
         # indentation slip at sac_imp.py:198-201); the drop-in always saves.
         torch.save(ck, path)
@@ -420,8 +493,17 @@ class SAC:
             self.log_alpha = ck["log_alpha"]
         if "alpha_optimizer_state_dict" in ck and self.automatic_entropy_tuning:
             self.alpha_optimizer.load_state_dict(ck["alpha_optimizer_state_dict"])
+        self._load_obs_norm(ck)
         if rows is not None:
-            self.replay_buffer._replace_arrays(*rows)
+            # the checkpoint's statistics already count these rows: frozen around the reload
+            mode, eps, clip = self._ctx.obs_norm()
+            if mode == 1:
+                self._ctx.set_obs_norm(2, eps, clip)
+            try:
+                self.replay_buffer._replace_arrays(*rows)
+            finally:
+                if mode == 1:
+                    self._ctx.set_obs_norm(1, eps, clip)
         return ck.get("episode", 0), ck.get("total_steps", 0)
 
     def _checkpoint_rows(self, rb):

@@ -295,6 +295,48 @@ class Context:
                ctypes.byref(n), ctypes.byref(total))
         return out[:n.value], int(total.value)
 
+    def set_obs_norm(self, mode: int = 1, eps: float = 1e-8, clip: float = 10.0) -> None:
+        """Running observation normalisation (sacmi.h sacmi_set_obs_norm): the ring keeps raw
+        observations; the update's gather and ``act`` normalise them with the running
+        statistics, ``clamp((x - mean) / sqrt(var + eps), -clip, clip)``.  ``mode`` 0: off,
+        1: on, pushes update the statistics, 2: on, frozen.  ``clip = math.inf``: none."""
+        L.call("sacmi_set_obs_norm", self._h, int(mode), float(eps), float(clip))
+
+    def obs_norm(self):
+        """(mode, eps, clip) in effect."""
+        mode, eps, clip = ctypes.c_int32(), ctypes.c_double(), ctypes.c_double()
+        L.call("sacmi_obs_norm", self._h, ctypes.byref(mode), ctypes.byref(eps), ctypes.byref(clip))
+        return int(mode.value), float(eps.value), float(clip.value)
+
+    def obs_norm_update(self, states) -> None:
+        """Rows of states [n, state_dim] into the running moments (any mode but off, frozen
+        included): e.g. terminal observations, which no stored transition has as its state."""
+        s = np.ascontiguousarray(states, np.float32).reshape(-1, self.cfg.state_dim)
+        L.call("sacmi_obs_norm_update", self._h, L.fptr(s) if s.size else None, s.shape[0])
+
+    def obs_norm_moments(self):
+        """(count, mean float64 [S], m2 float64 [S]): the running moments; m2 is the sum of
+        squared deviations from the mean (population variance = m2 / count).  Synchronises."""
+        S = self.cfg.state_dim
+        count = ctypes.c_double()
+        mean, m2 = np.zeros(S, np.float64), np.zeros(S, np.float64)
+        L.call("sacmi_obs_norm_get_moments", self._h, ctypes.byref(count), L.dptr(mean), L.dptr(m2), S)
+        return float(count.value), mean, m2
+
+    def set_obs_norm_moments(self, count: float, mean, m2) -> None:
+        mean = np.ascontiguousarray(mean, np.float64).reshape(-1)
+        m2 = np.ascontiguousarray(m2, np.float64).reshape(-1)
+        if mean.size != m2.size:
+            raise ValueError("mean and m2 differ in length")
+        L.call("sacmi_obs_norm_set_moments", self._h, float(count), L.dptr(mean), L.dptr(m2), mean.size)
+
+    def obs_norm_vectors(self):
+        """(nmean, nrstd) float32 [S]: the vectors the gather and ``act`` read."""
+        S = self.cfg.state_dim
+        nmean, nrstd = np.zeros(S, np.float32), np.zeros(S, np.float32)
+        L.call("sacmi_obs_norm_get_vectors", self._h, L.fptr(nmean), L.fptr(nrstd), S)
+        return nmean, nrstd
+
     def step_phase(self, batch: int, phase: int, grad_scale: float = 1.0, parity: int = 0,
                    have_batch: bool = False, ride_next: bool = False) -> None:
         if parity or have_batch or ride_next:

@@ -298,6 +298,61 @@ enum sacmi_gnorm { SACMI_GNORM_Q1 = 0, SACMI_GNORM_Q2 = 1, SACMI_GNORM_PI = 2, S
 /* as sacmi_fetch_stats: synchronises, most recent min(total, 4096, max_rows) rows oldest first */
 int sacmi_fetch_grad_norms(sacmi_ctx* ctx, float* out, int32_t max_rows, int32_t* n_out, int64_t* total);
 
+/* ---- running observation normalisation ------------------------------------------------ */
+/* The running mean / variance normaliser with clipping of the mainstream SAC stacks, with their
+ * semantics: the ring stores RAW observations; they are normalised where they are consumed — at
+ * sample time in the update's gather and at act time in sacmi_act — with the statistics current
+ * then.  The reference has none (replay_buffer.py:73).
+ *
+ * Running moments, per context, on the device, all fp64: count, mean[S] and M2[S] (the sum of
+ * squared deviations of column k from its mean).  They are updated from the state s of every
+ * transition a push actually stores (not s2; not the rows a push of more than `capacity` rows
+ * skips; sacmi_replay_clear leaves them alone) and from the rows handed to
+ * sacmi_obs_norm_update.  Each chunk of at most 1024 rows that reaches the device is merged
+ * into them (per-row Welford steps, Chan's merge; never E[x^2] - mean^2) in a fixed order
+ * without atomics: the same pushes from the same state give the same bits.
+ *
+ * Derived fp32 vectors, recomputed on the device whenever the moments or eps change:
+ *     nmean[k] = (float)mean[k]
+ *     nrstd[k] = (float)(1.0 / sqrt(M2[k] / count + eps))     population variance, fp64
+ * count == 0 is the identity (mean 0, scale 1).  (eps = 0 on a constant column gives an
+ * infinite scale and NaN rows: keep eps > 0.)
+ *
+ * The normalisation, one device function for every consumer, in fp32:
+ *     t = (x - nmean[k]) * nrstd[k]
+ *     y = t < -clip ? -clip : (t > clip ? clip : t)            a NaN stays a NaN
+ * applied to s and s2 of every gathered row and to the states of sacmi_act; the actions,
+ * rewards and done flags are untouched.  Under bf16 activations y is rounded to bf16 once,
+ * after normalising.  A NaN observation still surfaces as SACMI_ENAN from the policy sample.
+ *
+ * mode 0: off (default; the update's launches are exactly those of a context that never called
+ * this).  1: on, pushes update the moments.  2: on, frozen: pushes leave the moments alone
+ * (sacmi_obs_norm_update still counts).  eps >= 0 and finite, clip > 0 or +inf (no clipping),
+ * else SACMI_EVALUE.  On / off selects another captured graph; 1 <-> 2, the moments, eps and clip
+ * are stream-ordered device state: changing them re-captures nothing.  Switching off keeps the
+ * moments.
+ *
+ * On, the minibatch is gathered by a launch of its own in every update: no gather rides along
+ * in another update's launches and no batch is drawn ahead (sacmi_step_ride_possible reports
+ * 0), and while mode is 1 every pushed row takes the chunked device path (the push mailbox is
+ * bypassed).  sacmi_step_phase, sacmi_step_phase_ex and sacmi_step_dp return SACMI_ESTATE
+ * before touching state: each rank's shard would grow statistics of its own, and a collective
+ * over the moments is not built.
+ *
+ * SACMI_OBS_NORM=1 in the environment at sacmi_create selects mode 1 with eps 1e-8 and clip 10.
+ * Additive: the ABI version is unchanged. */
+int sacmi_set_obs_norm(sacmi_ctx* ctx, int32_t mode, double eps, double clip);
+int sacmi_obs_norm(sacmi_ctx* ctx, int32_t* mode, double* eps, double* clip);
+/* states [n][S] f32 into the moments; any mode but off (SACMI_ESTATE), "frozen" included */
+int sacmi_obs_norm_update(sacmi_ctx* ctx, const float* states, int64_t n);
+/* Synchronises the stream.  mean, m2: [S] f64, S = state_dim (else SACMI_EVALUE). */
+int sacmi_obs_norm_get_moments(sacmi_ctx* ctx, double* count, double* mean, double* m2, int32_t S);
+/* count < 0, m2 < 0, a non-finite value or a wrong S: SACMI_EVALUE.  Works in every mode. */
+int sacmi_obs_norm_set_moments(sacmi_ctx* ctx, double count, const double* mean, const double* m2,
+                               int32_t S);
+/* nmean, nrstd [S] f32 as the gather reads them (synchronises) */
+int sacmi_obs_norm_get_vectors(sacmi_ctx* ctx, float* nmean, float* nrstd, int32_t S);
+
 /* Data-parallel split of the step (one process per GPU).  phase 0: sample, gather,
  * forward, critic backward -> critic gradient buffer; phase 1: critic Adam + Polyak,
  * actor forward/backward -> actor gradient buffer; phase 2: actor Adam + alpha;
