@@ -234,10 +234,11 @@ __device__ __forceinline__ void mfma_chunk(f4 (&acc)[MT][NT], const float (&a)[M
 // With MG > 1 the workgroup covers MG*TM rows: wave group g = wave / KSPLIT takes rows
 // m0 + g*TM .. +TM, and the K split runs inside each group.
 // AXF 1: A-operand transform (GemmDesc::axk) applied to the loaded fragments before the
-// MFMAs: a(b,k) = A>0 ? coef[row]*w[k] : 0 with coef in LDS (coef[tile row]); with
-// store_a the transformed fragments are also written to d.ax_out.
+// MFMAs: a(b,k) = A>0 ? coef[row]*w[k] : 0 with coef in LDS (coef[tile row]).  STORE_A:
+// the core carries the side stores of the transformed fragments, which go to d.ax_out
+// where store_a holds; without STORE_A the core has no such store and forms no range.
 template <int TM, int TN, int KSPLIT, int G, bool AKC, bool BKC, bool ROWSUM, int MG = 1,
-          int AXF = 0, bool BF16 = false, bool A16 = false, class Pre>
+          int AXF = 0, bool BF16 = false, bool A16 = false, bool STORE_A = false, class Pre>
 __device__ __forceinline__ void gemm_core_l(const GemmDesc& d, int m0, int n0, float* red,
                                             float* rsum, Pre&& pre, bool store_a = false) {
   constexpr int MT = TM / 16, NT = TN / 16;
@@ -271,11 +272,12 @@ __device__ __forceinline__ void gemm_core_l(const GemmDesc& d, int m0, int n0, f
   const rsrc_t rxw = AXF == 1 ? make_rsrc(d.ax_w, (uint32_t)d.K * 4u)
                               : make_rsrc(d.a_ksc ? d.a_ksc : d.A, d.a_ksc ? (uint32_t)d.K * 4u : 0u);
   const bool has_ksc = AXF != 1 && d.a_ksc != nullptr;
-  // AXF 1 side output: unconditional stores, dropped by a zero-length range where this
+  // STORE_A side output: unconditional stores, dropped by a zero-length range where this
   // workgroup stores nothing (a guarded store makes the compiler's vmcnt bookkeeping
   // fall back to full drains)
-  const rsrc_t rAx = make_rsrc(store_a ? d.ax_out : d.C,
-                               store_a ? (uint32_t)(((size_t)(d.M - 1) * d.ax_ld + d.K) * 4) : 0u);
+  static_assert(!STORE_A || AXF == 1, "the side store is the A transform's");
+  const rsrc_t rAx = make_rsrc(STORE_A && store_a ? d.ax_out : d.C,
+                               STORE_A && store_a ? (uint32_t)(((size_t)(d.M - 1) * d.ax_ld + d.K) * 4) : 0u);
   if (nmine == 0) pre();
   for (int j = 0; j < nmine; j += G) {
 #pragma unroll
@@ -316,9 +318,11 @@ __device__ __forceinline__ void gemm_core_l(const GemmDesc& d, int m0, int n0, f
             for (int s = 0; s < 4; ++s)
               a[g][i][s] = (a[g][i][s] > 0.f && k + s < d.K) ? xw[g][s] : 0.f;
             // the rows this level's tile-0 workgroups hold in full: u for a later level
-            const int rr = m0 - mloc + r;
-            buf_st4(rAx, (rr < d.M && k < d.K) ? (uint32_t)(rr * d.ax_ld + k) * 4u : 0xfffffff0u,
-                    f4{a[g][i][0], a[g][i][1], a[g][i][2], a[g][i][3]});
+            if constexpr (STORE_A) {
+              const int rr = m0 - mloc + r;
+              buf_st4(rAx, (rr < d.M && k < d.K) ? (uint32_t)(rr * d.ax_ld + k) * 4u : 0xfffffff0u,
+                      f4{a[g][i][0], a[g][i][1], a[g][i][2], a[g][i][3]});
+            }
           }
         } else if constexpr (!AKC) {
           // A K-scale (selected, not branched: 1 where the desc has none)
@@ -385,14 +389,31 @@ __device__ __forceinline__ void place_tile(const GemmDesc& d, int t, int& tr, in
 // A row-prologue level has the one core: fc3 backward folded into dh1 / dha1 (A = h2
 // transformed, B = W2).  (Layout dispatch: wave-uniform, once per workgroup.)
 //   kRowsTile64W the same with the rows' importance-sampling weights (kWgtAlways)
-constexpr int kRowsNone = 0, kRowsTile64 = 1, kRowsSpread = 2, kRowsTile64W = 3;
+//   kRowsDw      no transform either, and the level is a weight-gradient level (dw_level, on
+//                the host): every desc has both operands row-contiguous, so only the two
+//                row-contiguous cores (with and without the row sums) are compiled
+// The fp32 spread form picks its core once per workgroup by whether the workgroup stores u
+// (gemm_core_l STORE_A); its bf16 twin (three more SGPR spills with two cores) and the
+// 64-row forms keep the one core with the range-dropped stores.
+constexpr int kRowsNone = 0, kRowsTile64 = 1, kRowsSpread = 2, kRowsTile64W = 3, kRowsDw = 4;
 constexpr bool rows_tile64(int rows) { return rows == kRowsTile64 || rows == kRowsTile64W; }
+constexpr bool rows_ax(int rows) { return rows != kRowsNone && rows != kRowsDw; }
 template <int TM, int TN, int KSPLIT, int G, int MG, int ROWS, bool BF16, class Pre>
 __device__ __forceinline__ void gemm_core(const GemmDesc& d, int m0, int n0, float* red,
                                           float* rsum, bool rowsum, Pre&& pre) {
-  if constexpr (ROWS != kRowsNone) {
-    gemm_core_l<TM, TN, KSPLIT, G, true, false, false, MG, 1, BF16>(d, m0, n0, red, rsum, pre,
-                                                                  n0 == 0 && d.ax_out != nullptr);
+  if constexpr (ROWS == kRowsSpread && !BF16) {
+    if (n0 == 0 && d.ax_out != nullptr)
+      gemm_core_l<TM, TN, KSPLIT, G, true, false, false, MG, 1, BF16, false, true>(d, m0, n0, red, rsum, pre, true);
+    else
+      gemm_core_l<TM, TN, KSPLIT, G, true, false, false, MG, 1, BF16, false, false>(d, m0, n0, red, rsum, pre);
+    return;
+  } else if constexpr (rows_ax(ROWS)) {
+    gemm_core_l<TM, TN, KSPLIT, G, true, false, false, MG, 1, BF16, false, true>(d, m0, n0, red, rsum, pre,
+                                                                               n0 == 0 && d.ax_out != nullptr);
+    return;
+  } else if constexpr (ROWS == kRowsDw) {
+    if (rowsum) gemm_core_l<TM, TN, KSPLIT, G, false, false, true, MG, 0, BF16>(d, m0, n0, red, rsum, pre);
+    else gemm_core_l<TM, TN, KSPLIT, G, false, false, false, MG, 0, BF16>(d, m0, n0, red, rsum, pre);
     return;
   }
   if (d.a_kc) {
@@ -1026,7 +1047,7 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
                                         KgSmem<TM, TN, KSPLIT, MG, ROWS>& sm) {
   // AX: a row-prologue level (every desc a plain dh desc with the A transform); SPREAD: its
   // 32x32 one-wave-group form, which also forms the dL/da partials (PA)
-  constexpr bool AX = ROWS != kRowsNone, SPREAD = ROWS == kRowsSpread, PA = SPREAD;
+  constexpr bool AX = rows_ax(ROWS), SPREAD = ROWS == kRowsSpread, PA = SPREAD;
   constexpr int WGT = ROWS == kRowsTile64W ? kWgtAlways : kWgtNone;   // (the 64-row form's)
   static_assert(!AX || !ADAM, "a row-prologue level has no fused Adam");
   static_assert(!SPREAD || MG == 1, "the spread prologue: one wave group");
@@ -3099,11 +3120,12 @@ static int fwd_big_ok(GemmBatch& b) {
   return fwd_level_tiles(b) ? 0 : -1;
 }
 
-// one k_gemm configuration, fp32 or bf16 MFMA operands
-template <int TM, int TN, int KSPLIT, int G, int MG, bool ADAM, int ROWS>
+// one k_gemm configuration, fp32 or bf16 MFMA operands (ROWS16: the bf16 kernel's form
+// where it keeps another than the fp32 one)
+template <int TM, int TN, int KSPLIT, int G, int MG, bool ADAM, int ROWS, int ROWS16 = ROWS>
 static void launch_k(GemmBatch& b, int grid, hipStream_t s) {
   const dim3 blk(64 * KSPLIT * MG);
-  if (b.bf16) hipLaunchKernelGGL((k_gemm<TM, TN, KSPLIT, G, MG, ADAM, ROWS, true>), dim3(grid), blk, 0, s, b);
+  if (b.bf16) hipLaunchKernelGGL((k_gemm<TM, TN, KSPLIT, G, MG, ADAM, ROWS16, true>), dim3(grid), blk, 0, s, b);
   else hipLaunchKernelGGL((k_gemm<TM, TN, KSPLIT, G, MG, ADAM, ROWS, false>), dim3(grid), blk, 0, s, b);
   HIP_LAUNCH_CHECK();
 }
@@ -3244,6 +3266,15 @@ static void launch_fwd_x6(GemmBatch& b, int, hipStream_t s) {
   HIP_LAUNCH_CHECK();
 }
 
+// Whether the level is a weight-gradient level: every desc has both operands row-contiguous
+// (dW = dY^T X: A and B are both read down the batch).  k_gemm compiles such a level with the
+// row-contiguous cores alone (kRowsDw).  A fused-Adam level is always one.
+static bool dw_level(const GemmBatch& b) {
+  bool dw = true;
+  for (int i = 0; i < b.count; ++i) dw = dw && !b.d[i].a_kc && !b.d[i].b_kc;
+  return dw;
+}
+
 // Whether the level is a row-prologue level: no desc has the A transform (false), or every
 // desc is a plain dh desc with it — axk 1, ReLU-mask epilogue, no bias, no bias-gradient
 // column, no dot partials, no A K-scale — behind a critic or actor prologue (true).  Anything
@@ -3313,12 +3344,15 @@ static GemmPlan plan_gemm_level(const GemmBatch& b0) {
   // (Level::add guarantees a level is all-Adam or all-plain)
   // weight-gradient levels (both operands row-contiguous): the Adam-fused and the plain
   // (data-parallel) form of a level take the same tile geometry, so their bits agree
-  bool dw = true;
-  for (int i = 0; i < b.count; ++i) dw = dw && !b.d[i].a_kc && !b.d[i].b_kc;
+  const bool dw = dw_level(b);
+  // (the fused-Adam kernels carry the row-contiguous cores only.  Two of them keep the
+  // dispatching form, which for a dW level runs the same two cores: with the two cores alone
+  // the bf16 32x64x16 one gains 12 B of scratch and the fp32 64x64 one 8 B.)
+  if (n_adam && !dw) throw Error{SACMI_ESTATE, "fused Adam on a level that is not a weight-gradient level"};
   const int t64 = assign_tiles<32, 64>(b);
   if (dw && t64 <= 256) {
     // one 32x64 tile per CU (policy level): 16 waves, K split 16 ways
-    pl.launch = n_adam ? launch_k<32, 64, 16, 1, 1, true, kRowsNone> : launch_k<32, 64, 16, 1, 1, false, kRowsNone>;
+    pl.launch = n_adam ? launch_k<32, 64, 16, 1, 1, true, kRowsDw, kRowsNone> : launch_k<32, 64, 16, 1, 1, false, kRowsDw>;
     pl.arg = b.total_tiles + extra;
   } else if (dw || n_adam || t64 > 512) {
     // more 32x64 tiles than CUs (the twin critic weight gradients; every level at large
@@ -3334,8 +3368,8 @@ static GemmPlan plan_gemm_level(const GemmBatch& b0) {
     if (rows && extra) throw Error{SACMI_ESTATE, "ride on a row-prologue level of 64-row tiles"};
     // (a row-prologue level is neither dW nor Adam)
     pl.rows = rows ? (b.rows.w ? kRowsTile64W : kRowsTile64) : kRowsNone;
-    if (n_adam) pl.launch = launch_k<32, 64, 8, 1, 2, true, kRowsNone>;
-    else if (dw) pl.launch = launch_k<32, 64, 8, 1, 2, false, kRowsNone>;   // the plain (data-parallel) form
+    if (n_adam) pl.launch = launch_k<32, 64, 8, 1, 2, true, kRowsNone, kRowsDw>;
+    else if (dw) pl.launch = launch_k<32, 64, 8, 1, 2, false, kRowsDw>;   // the plain (data-parallel) form
     else if (rows && b.rows.w) pl.launch = launch_k<32, 64, 4, 1, 2, false, kRowsTile64W>;
     else if (rows) pl.launch = launch_k<32, 64, 4, 1, 2, false, kRowsTile64>;
     else if (!extra) pl.launch = launch_k<32, 64, 4, 1, 2, false, kRowsNone>;

@@ -1614,35 +1614,45 @@ static void enqueue_many(sacmi_ctx* c, int B, int dev_idx, int dev_eps, bool use
   }
 }
 
-static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_mask,
-                       float grad_scale, bool use_ring, int reps = 1, PhaseRide pr = {}) {
+// What one launch of run_update puts on the stream (its graph's content).  Consecutive fused
+// updates hand the next update's sampling + gather to ride-along workgroups of the current one
+static void enqueue_launch(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_mask,
+                           float grad_scale, bool use_ring, int reps, const PhaseRide& pr) {
+  if (phase_mask == 5) {   // phase 2 of the previous update, then phase 0 of the next
+    enqueue_update(c, B, dev_idx, dev_eps, 4, grad_scale, use_ring, pr.parity ^ 1);
+    enqueue_update(c, B, dev_idx, dev_eps, 1, grad_scale, use_ring, pr.parity, pr.have_batch);
+    return;
+  }
+  if (phase_mask != 7) {   // one phase of a split update
+    enqueue_update(c, B, dev_idx, dev_eps, phase_mask, grad_scale, use_ring, pr.parity,
+                   pr.have_batch, pr.ride_next);
+    return;
+  }
+  if (reps == 1 && (pr.ride_next || pr.have_batch)) {   // one fused update drawing the next one's batch ahead
+    c->pf_save = true;
+    enqueue_update(c, B, dev_idx, dev_eps, 7, grad_scale, use_ring, pr.parity, pr.have_batch, pr.ride_next);
+    c->pf_save = false;
+    return;
+  }
+  enqueue_many(c, B, dev_idx, dev_eps, use_ring, reps, pr);
+}
+
+// what run_update does before it enqueues (before any state changes; enqueue_update)
+static void begin_update(sacmi_ctx* c, int dev_idx, int phase_mask) {
   REQUIRE(!c->per_feedback || (dev_idx && phase_mask == 7), SACMI_ESTATE,
           "prioritized feedback is on: the update samples on the device (no staged indices, "
           "no phase-split or data-parallel update)");
-  if (phase_mask & 6) require_moments_whole(c);   // (before any state changes; enqueue_update)
+  if (phase_mask & 6) require_moments_whole(c);
   c->pf_save = false;
   if (!c->mb_graph) mb_flush(c);   // (mb_graph: this update's sampler takes them)
   c->inflight = true;
-  // consecutive fused updates hand the next update's sampling + gather to ride-along
-  // workgroups of the current one
+}
+
+static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_mask,
+                       float grad_scale, bool use_ring, int reps = 1, PhaseRide pr = {}) {
+  begin_update(c, dev_idx, phase_mask);
   auto enqueue_all = [&]() {
-    if (phase_mask == 5) {   // phase 2 of the previous update, then phase 0 of the next
-      enqueue_update(c, B, dev_idx, dev_eps, 4, grad_scale, use_ring, pr.parity ^ 1);
-      enqueue_update(c, B, dev_idx, dev_eps, 1, grad_scale, use_ring, pr.parity, pr.have_batch);
-      return;
-    }
-    if (phase_mask != 7) {   // one phase of a split update
-      enqueue_update(c, B, dev_idx, dev_eps, phase_mask, grad_scale, use_ring, pr.parity,
-                     pr.have_batch, pr.ride_next);
-      return;
-    }
-    if (reps == 1 && (pr.ride_next || pr.have_batch)) {   // one fused update drawing the next one's batch ahead
-      c->pf_save = true;
-      enqueue_update(c, B, dev_idx, dev_eps, 7, grad_scale, use_ring, pr.parity, pr.have_batch, pr.ride_next);
-      c->pf_save = false;
-      return;
-    }
-    enqueue_many(c, B, dev_idx, dev_eps, use_ring, reps, pr);
+    enqueue_launch(c, B, dev_idx, dev_eps, phase_mask, grad_scale, use_ring, reps, pr);
   };
   // the caller is capturing this stream into its own graph (e.g. torch.cuda.graph around
   // a data-parallel update and its collectives): enqueue into that capture directly
@@ -3384,14 +3394,14 @@ int sacmi_profile_sites(sacmi_ctx* c, int32_t batch, int32_t reps, char* names_o
 
 // Launch timeline of whatever `enqueue` puts on the context stream, captured into one
 // hipGraph with every kernel launch pointing at its own timeline slots; replayed once
-// warm, then once measured between HIP events.  Sites that launch no stamping kernel (the
+// warm (unless !warm), then once measured between HIP events.  Sites that launch no stamping kernel (the
 // RCCL all-reduces of the data-parallel sequence) leave no entry.
 extern "C++" {
 template <class F>
 static void timeline_of(sacmi_ctx* c, int n_updates, F&& enqueue, int32_t max_kernels,
                         char* names_out, int32_t* kind_out, int32_t* grid_out, int32_t* site_out,
                         double* start_us, double* end_us, double* flops_out, double* bytes_out,
-                        int32_t* n_kernels, double* graph_us) {
+                        int32_t* n_kernels, double* graph_us, bool warm = true) {
   REQUIRE(max_kernels > 0 && names_out && kind_out && grid_out && site_out && start_us && end_us &&
               n_kernels && graph_us, SACMI_EVALUE, "null output");
   CHECK_HIP(hipStreamSynchronize(c->stream));
@@ -3414,7 +3424,7 @@ static void timeline_of(sacmi_ctx* c, int n_updates, F&& enqueue, int32_t max_ke
     c->tl_dev = nullptr; c->tl_cur = nullptr;
     CHECK_HIP(hipEventCreate(&e0));
     CHECK_HIP(hipEventCreate(&e1));
-    CHECK_HIP(hipGraphLaunch(ex, c->stream));     // warm (its stamps are discarded)
+    if (warm) CHECK_HIP(hipGraphLaunch(ex, c->stream));     // (its stamps are discarded)
     CHECK_HIP(hipMemsetAsync(buf.p, 0xFF, buf.n * sizeof(tl_word), c->stream));
     CHECK_HIP(hipEventRecord(e0, c->stream));
     CHECK_HIP(hipGraphLaunch(ex, c->stream));
@@ -3485,6 +3495,24 @@ int sacmi_profile_timeline(sacmi_ctx* c, int32_t batch, int32_t n_updates, int32
     // the same update sequence sacmi_step_many_async replays
     timeline_of(c, n_updates, [&]() { enqueue_many(c, batch, 1, 1, true, n_updates); }, max_kernels, names_out, kind_out, grid_out, site_out, start_us, end_us, flops_out,
        bytes_out, n_kernels, graph_us);
+  });
+}
+
+int sacmi_profile_launch_timeline(sacmi_ctx* c, int32_t batch, int32_t n_updates, int32_t max_kernels,
+                                  char* names_out, int32_t* kind_out, int32_t* grid_out, int32_t* site_out,
+                                  double* start_us, double* end_us, double* flops_out, double* bytes_out,
+                                  int32_t* n_kernels, double* graph_us) {
+  return guard([&] {
+    check_device_batch(c, batch);
+    REQUIRE(n_updates >= 1 && n_updates <= 256, SACMI_EVALUE, "n_updates must be in [1, 256]");
+    // sacmi_step_many_async itself, its graph captured with the stamps and launched once: it
+    // takes a batch drawn ahead and draws the next launch's exactly as that call would now
+    const PhaseRide pr = pf_begin(c, batch, true);
+    begin_update(c, 1, 7);
+    timeline_of(c, n_updates, [&]() { enqueue_launch(c, batch, 1, 1, 7, 1.f, true, n_updates, pr); },
+                max_kernels, names_out, kind_out, grid_out, site_out, start_us, end_us, flops_out,
+                bytes_out, n_kernels, graph_us, false);
+    pf_end(c, batch, pr, n_updates);
   });
 }
 

@@ -130,6 +130,9 @@ _PROTOS = {
     "sacmi_profile_timeline": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
                                c_i32p, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p,
                                c_f64p],
+    "sacmi_profile_launch_timeline": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
+                                      c_i32p, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p,
+                                      c_f64p],
     "sacmi_profile_timeline_dp": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
                                   c_i32p, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p,
                                   c_f64p],

@@ -542,6 +542,16 @@ int sacmi_profile_timeline(sacmi_ctx* ctx, int32_t batch, int32_t n_updates, int
                            double* start_us, double* end_us, double* flops_out, double* bytes_out,
                            int32_t* n_kernels, double* graph_us);
 
+/* The timeline of ONE real launch: sacmi_step_many_async(batch, n_updates) as it would run
+ * now, captured with the stamps and launched once (no warm-up replay).  It takes a batch the
+ * previous launch drew ahead (then it has no sampler / gather launch of its own) and draws the
+ * next launch's, exactly as that call does: the state advances by n_updates updates, bit for
+ * bit as sacmi_step_many_async's.  Outputs as sacmi_profile_timeline. */
+int sacmi_profile_launch_timeline(sacmi_ctx* ctx, int32_t batch, int32_t n_updates, int32_t max_kernels,
+                                  char* names_out, int32_t* kind_out, int32_t* grid_out, int32_t* site_out,
+                                  double* start_us, double* end_us, double* flops_out, double* bytes_out,
+                                  int32_t* n_kernels, double* graph_us);
+
 /* sacmi_profile_timeline over the data-parallel sequence sacmi_step_dp replays (phases +
  * the two RCCL all-reduces of every update; needs sacmi_allreduce_init, and every rank of
  * the communicator must make the same call, since the captured graph holds the
