@@ -518,8 +518,10 @@ __device__ __forceinline__ uint32_t s_ld(sbuf_i4 r, uint32_t byte_off) {
 // The fused-Adam level's scalar work (losses, the alpha step, the loss ring, the done word),
 // by ONE wave, on wave-uniform values read by scalar loads (s_ld).  Every value it reads
 // was written by an earlier level, and nothing of the level reads what it writes, so it
-// runs at the level's start (k_gemm: wave 0 of block 0 before its tile) — after the tile it made block 0 the level's last workgroup by 2.7-2.9 us (a chain
-// of dependent round trips, then a system-scope fence; phase stamps, profiles/r04).
+// runs at the level's start (k_gemm: wave 0 of the first gather-ride workgroup where one rides,
+// else wave 0 of block 0 before its tile, kg_body) — after the tile it made block 0 the level's
+// last workgroup by 2.7-2.9 us (a chain of dependent round trips, then a system-scope fence;
+// phase stamps, profiles/r04).  loss_host / done_word: the synchronous forms' graphs only.
 __device__ __forceinline__ void adam_block0_wave(const AdamFuse& af, int err, float omb1, float omb2) {
   const sbuf_i4 rLp = s_rsrc(af.loss_part), rSc = s_rsrc(af.sc);
   const bool alpha = af.log_alpha_idx >= 0 && af.auto_entropy;
@@ -1035,6 +1037,12 @@ struct KgSmem {
   float s_pa[PA ? TMW * (TN + 1) + TN * 32 : 1];
 };
 
+// A fused-Adam k_gemm level whose scalar chain (adam_block0_wave) runs on the first gather-ride
+// workgroup instead of block 0 (1024-thread configurations: the ones that carry rides)
+__device__ __forceinline__ bool chain_rides(const GemmBatch& b) {
+  return b.ride.kind == 2 && b.ride.nblocks > 0;
+}
+
 // The body of one k_gemm workgroup: work item `bid` of the level (a tile, a ride-along
 // workgroup, the scalar Adam workgroup).  Its pieces, in order (the ---- marks): locating
 // the work; prefetching the epilogue's operands (pre(), which gemm_core_l runs behind the
@@ -1090,6 +1098,23 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   auto& s_dotw = sm.s_dotw;
   // dL/da partials (PA): the tile's outputs [TMW][TN+1] and its fc1 action weights [TN][32]
   float* const s_pa = sm.s_pa;
+  if constexpr (ADAM) {
+    // The level's scalar Adam work first (adam_block0_wave), on ONE wave.  Where a gather rides
+    // (L13 of an update that has a successor; 1024-thread configurations carry the rides): wave
+    // 0 of the first ride workgroup, in front of its one gather row — a wave that owns no tile.
+    // On wave 0 of block 0 the chain (~4 us: dependent scalar round trips, the fp64 bias
+    // corrections, the ring slot's 64-bit modulo) made block 0 the level's last workgroup by
+    // ~1 us at batch 256, where every wave has one K chunk and nothing hides it
+    // (profiles/async_scalars).  Otherwise wave 0 of block 0, before its tile: the other waves
+    // start their K loops, wave 0 follows, inside the tile's time where the K loop is long
+    const bool rides = gemm_threads<KSPLIT, MG>() == 1024 && chain_rides(batch);
+    if (bid == (rides ? n_tiles : 0) && threadIdx.x < 64) {
+      const AdamFuse& a = batch.adam;
+      adam_block0_wave(a, (int)s_ld(s_rsrc(a.sc), (uint32_t)offsetof(DevScalars, err)), 1.f - a.beta1,
+                       1.f - a.beta2);
+      if (rides) SACMI_PHASE(tl, 2);   // (diagnostic: the chain's end on the ride workgroup)
+    }
+  }
   if (bid >= n_tiles) {   // ride-along workgroups (next update's replay work, Polyak)
     if constexpr (gemm_threads<KSPLIT, MG>() == 1024) {   // the host attaches rides to 1024-thread configs
       const int rb = bid - n_tiles;
@@ -1147,15 +1172,6 @@ __device__ __forceinline__ void kg_body(const GemmBatch& batch, const int bid,
   place_tile(d, t, tr, tc);
   const int m0 = tr * TMW, n0 = tc * TN;
   SACMI_PHASE(batch.tl, 9);   // (diagnostic: the tile is placed)
-  if constexpr (ADAM) {
-    // the level's scalar Adam work first, on wave 0 of block 0 (adam_block0_wave): the
-    // other waves start their K loops, wave 0 follows ~3 us later, inside the tile's time
-    if (bid == 0 && threadIdx.x < 64) {
-      const AdamFuse& a = batch.adam;
-      adam_block0_wave(a, (int)s_ld(s_rsrc(a.sc), (uint32_t)offsetof(DevScalars, err)), 1.f - a.beta1,
-                       1.f - a.beta2);
-    }
-  }
   const bool rowsum = !AX && d.rs_col >= 0 && n0 == 0;
   const AdamFuse& af = batch.adam;
   // Element slots: EPT tile outputs per thread (e = tid + s*NTH) plus one slot for the

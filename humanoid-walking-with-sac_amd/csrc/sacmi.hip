@@ -1156,6 +1156,12 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
   float* G = c->G.p;
   const float* T = c->T.p;
   const int nb = (B + 31) / 32;     // loss partials: one per 32-row block of L5 / L9
+  // Fused updates whose losses leave through the ring (sacmi_step_async, _many_async, the
+  // one-rank sacmi_step_dp, the timeline's replicas; use_ring is part of the graph key): nobody
+  // reads the host-mapped loss / error / done words (step_finish alone does, and it follows
+  // the synchronous forms' graphs only), so these graphs store none of them: no store over
+  // the host link and no system-scope fence in the fused levels' scalar chains
+  const bool ring_only = use_ring && phase_mask == 7;
   auto W = [&](const Linear& l) { return P + l.off; };
   // fc3 dot partials: slot 0/1 q1/q2 (L2), 2/3 target q1/q2 (L4), 4/5 updated q1/q2 (L8)
   auto dotp = [&](int slot) { return c->dotp.p + (size_t)slot * B * c->nparts; };
@@ -1326,7 +1332,7 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
       f.lr = (float)c->cfg.lr; f.beta1 = 0.9f; f.beta2 = 0.999f; f.eps = 1e-8f;
       f.tau = (float)c->cfg.tau; f.step_offset = 1; f.sc = c->sc.p;
       f.loss_part = c->lpart_c.p; f.n_part = nb; f.loss_slot0 = 0; f.n_losses = 2;
-      f.loss_host = c->loss_host_dev;
+      f.loss_host = ring_only ? nullptr : c->loss_host_dev;
       f.Ph = c->Ph.p; f.Th = c->Th.p;
       f.loss_div = (float)B; f.log_alpha_idx = -1; f.auto_entropy = 0;
       f.err_skip = kErrSkipAll; f.err_nopolyak = kErrActLike;
@@ -1351,7 +1357,7 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
     if (polyak_ride) { ad.tgt = nullptr; ad.tgth = nullptr; }   // (Polyak: in L12)
     if (phase_mask == 7) {   // the clipped single-GPU update: in L6's place (no collective, no
       ad.err_flags = nullptr;             // flags; the early error word for the synchronous step)
-      ad.loss_host = c->loss_host_dev;
+      ad.loss_host = ring_only ? nullptr : c->loss_host_dev;
     }
     const char* name = polyak_ride ? "adam_critic" : "adam_critic_polyak";
     if (c->clip_on) {
@@ -1471,12 +1477,12 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
       f.lr = (float)c->cfg.lr; f.beta1 = 0.9f; f.beta2 = 0.999f; f.eps = 1e-8f; f.tau = 0.f;
       f.step_offset = 0; f.sc = c->sc.p;
       f.loss_part = c->lpart_a.p; f.n_part = nb; f.loss_slot0 = 2; f.n_losses = 1;
-      f.loss_host = c->loss_host_dev;
+      f.loss_host = ring_only ? nullptr : c->loss_host_dev;
       f.Ph = c->Ph.p; f.Th = c->Th.p;
       f.loss_div = (float)B; f.log_alpha_idx = c->la_idx; f.auto_entropy = c->cfg.auto_entropy;
       f.log_alpha_grad = G + c->la_idx;
       f.loss_ring = use_ring ? c->ring.p : nullptr; f.ring = c->ring_slots;
-      f.done_word = reinterpret_cast<int*>(c->loss_host_dev + 4);
+      f.done_word = ring_only ? nullptr : reinterpret_cast<int*>(c->loss_host_dev + 4);
       f.err_skip = ~0; f.err_nopolyak = 0;
     }
     if (polyak_ride) {   // (polyak_ride: the critic Adam above left the targets alone)
@@ -1521,9 +1527,9 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
   }
   if ((phase_mask & 4) && (phase_mask != 7 || c->clip_on)) {
     AdamArgs ad = dp_adam_args(c, false, B, grad_scale, use_ring);
-    if (phase_mask == 7) {   // the clipped single-GPU update: in L13's place, the update's last
-      ad.loss_host = c->loss_host_dev;    // scalar work (the synchronous step's losses and done word)
-      ad.done_word = reinterpret_cast<int*>(c->loss_host_dev + 4);
+    if (phase_mask == 7 && !ring_only) {   // the clipped single-GPU update: in L13's place, the
+      ad.loss_host = c->loss_host_dev;     // update's last scalar work (the synchronous step's
+      ad.done_word = reinterpret_cast<int*>(c->loss_host_dev + 4);   // losses and done word)
     }
     if (c->clip_on) {
       enqueue_clip_adam(c, ad, false, "adam_actor_alpha", s);
@@ -2195,6 +2201,16 @@ int sacmi_synchronize(sacmi_ctx* c) {
     CHECK_HIP(hipStreamSynchronize(c->stream));
     c->inflight = false;
     c->done_epoch = c->epoch;
+  });
+}
+
+int sacmi_debug_host_words(sacmi_ctx* c, uint32_t out[5]) {
+  return guard([&] {
+    REQUIRE(c && out, SACMI_EVALUE, "null argument");
+    // (the stream alone: the context's own bookkeeping — inflight, done_epoch — stays as it is,
+    // so the next synchronous step takes the path it would have taken)
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    std::memcpy(out, c->loss_host, 20);
   });
 }
 

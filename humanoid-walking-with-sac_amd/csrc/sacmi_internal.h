@@ -315,6 +315,8 @@ struct AdamFuse {
   int64_t log_alpha_idx; int auto_entropy;   // scalar alpha Adam (step idx 3), -1: none
   const float* log_alpha_grad;               // written by k_critic_rows
   float* loss_ring; int ring;
+  // host-mapped words: the synchronous forms' graphs only (sacmi_step, sacmi_step_launch /
+  // _wait).  Updates whose losses leave through the ring store nothing over the host link
   float* loss_host;      // or null: the losses also stored to host-mapped memory (sync step);
                          //   block 0 stores sc->err's bits into word 3
   int* done_word;        // or null (host-mapped): the update's last level, after everything

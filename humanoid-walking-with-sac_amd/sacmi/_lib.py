@@ -91,6 +91,7 @@ _PROTOS = {
     "sacmi_read_backward": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int64],
     "sacmi_read_batch": [c_vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), c_f32p, ctypes.c_int64],
     "sacmi_fetch_losses": [c_vp, c_f32p, ctypes.c_int32, c_i32p],
+    "sacmi_debug_host_words": [c_vp, c_u32p],
     "sacmi_set_stats": [c_vp, ctypes.c_int32],
     "sacmi_stats": [c_vp, c_i32p],
     "sacmi_fetch_stats": [c_vp, c_f32p, ctypes.c_int32, c_i32p, c_i64p],

@@ -251,6 +251,14 @@ class Context:
         L.call("sacmi_fetch_losses", self._h, L.fptr(out), int(max_steps), ctypes.byref(n))
         return out[:n.value]
 
+    def debug_host_words(self) -> np.ndarray:
+        """Test hook (sacmi.h sacmi_debug_host_words): the synchronous step's five host-mapped
+        words as uint32 — the bits of q1_loss, q2_loss, policy_loss, the error bits, the done
+        counter."""
+        out = np.zeros(5, np.uint32)
+        L.call("sacmi_debug_host_words", self._h, L.u32ptr(out))
+        return out
+
     def set_stats(self, on: bool = True) -> None:
         """Per-update diagnostics (sacmi.h sacmi_set_stats): on, every update appends one row
         of ``L.STAT_NAMES`` values, reduced on the device, to a ring of 4096 rows."""

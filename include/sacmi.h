@@ -204,7 +204,9 @@ int sacmi_step(sacmi_ctx* ctx, int32_t batch, const int64_t* idx, const float* e
 int sacmi_step_launch(sacmi_ctx* ctx, int32_t batch);
 int sacmi_step_wait(sacmi_ctx* ctx, float* losses_out);
 /* Same work, enqueued only (no host sync, no host writes); losses stay on device
- * in a ring of `ring` slots, fetched by sacmi_fetch_losses. */
+ * in a ring of `ring` slots, fetched by sacmi_fetch_losses.  The host-mapped loss, error and
+ * done words are maintained by the synchronous forms only (sacmi_step, sacmi_step_launch /
+ * _wait): the async forms' kernels store nothing into host memory. */
 int sacmi_step_async(sacmi_ctx* ctx, int32_t batch);
 /* n_updates consecutive updates (device indices + device noise) as ONE launch: the
  * `for _ in range(updates_per_step): agent.update_parameters(batch_size)` loop of
@@ -407,6 +409,13 @@ enum sacmi_backward_buf { SACMI_BWD_DHC = 0, SACMI_BWD_DHA = 1, SACMI_BWD_DHP = 
                           SACMI_BWD_DQ4 = 4, SACMI_BWD_DHEAD = 5, SACMI_BWD_DOTP = 6 };
 int sacmi_read_backward(sacmi_ctx* ctx, int32_t which, int32_t layer, int32_t batch, float* out,
                         int64_t numel);
+/* Test hook (read-only: synchronises the stream and copies, launches nothing, and leaves the
+ * context's own bookkeeping alone): the five host-mapped words of the synchronous step —
+ * out[0..2] the bits of {q1_loss, q2_loss, policy_loss}, out[3] the error bits, out[4] the done
+ * counter.  They are maintained by the synchronous forms only (sacmi_step, sacmi_step_launch /
+ * _wait): sacmi_step_async, sacmi_step_many_async and the one-rank sacmi_step_dp store none of
+ * them.  Additive: the ABI version is unchanged. */
+int sacmi_debug_host_words(sacmi_ctx* ctx, uint32_t out[5]);
 /* Test hook: the minibatch of the last device-sampled update of `batch` rows that used batch
  * set 0 (every single update, and the first of a multi-update graph): its replay indices
  * (idx[batch]: deque positions, or ring slots for PER) and the policy noise it drew
