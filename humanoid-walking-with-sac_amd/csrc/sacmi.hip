@@ -297,6 +297,15 @@ struct sacmi_ctx {
   sacmi::DevBuf<float> on_vec, on_actx;
   int on_mode = 0;
   double on_eps = 1e-8, on_clip = 10.0;
+  // sacmi_set_nstep (nstep.hip): the steps (1: off), the gather's table + steps word ns_tab
+  // [kNStepMax floats | n], the ring's episode-end flags ep_end [capacity], and the flags'
+  // staging beside the push's (same slots, same reuse protocol); allocated when first needed
+  int nstep = 1;
+  sacmi::DevBuf<float> ns_tab;
+  sacmi::DevBuf<uint8_t> ep_end, ep_stage;
+  uint8_t* ep_host[2] = {};
+  uint8_t* ep_zc_host[2] = {};
+  uint8_t* ep_zc_dev[2] = {};
   std::map<sacmi::GraphKey, hipGraphExec_t> graphs;
   bool use_graphs = true;
   bool G_external = false;
@@ -602,6 +611,9 @@ static void free_pinned(sacmi_ctx* c) {
     c->push_ev[i] = nullptr;
     c->push_host[i] = nullptr;
     if (c->push_zc_host[i]) (void)hipHostFree(c->push_zc_host[i]);
+    if (c->ep_host[i]) (void)hipHostFree(c->ep_host[i]);
+    if (c->ep_zc_host[i]) (void)hipHostFree(c->ep_zc_host[i]);
+    c->ep_host[i] = nullptr; c->ep_zc_host[i] = nullptr; c->ep_zc_dev[i] = nullptr;
     if (i == 0 && c->mb_host) (void)hipHostFree(c->mb_host);
     if (i == 0) { c->mb_host = nullptr; c->mb_dev = nullptr; }
     c->push_zc_host[i] = nullptr;
@@ -890,9 +902,17 @@ static ObsNormArgs obs_norm_args(const sacmi_ctx* c) {
   return ObsNormArgs{c->on_vec.p, c->on_vec.p + Sp, c->on_vec.p + 2 * Sp};
 }
 
+// N-step returns on: as above — NStepArgs is a kernel parameter of the gather's own
+static bool nstep_on(const sacmi_ctx* c) { return c->nstep >= 2; }
+static NStepArgs nstep_args(const sacmi_ctx* c) {
+  return NStepArgs{reinterpret_cast<const int32_t*>(c->ns_tab.p + kNStepMax), c->ns_tab.p, c->ep_end.p};
+}
+// the update launches a gather of its own: none rides, none is drawn ahead
+static bool own_gather(const sacmi_ctx* c) { return obs_norm_on(c) || nstep_on(c); }
+
 // Can the next update's sampling + gather ride along in this update's launches?
 static bool ride_possible(sacmi_ctx* c, int B) {
-  return !obs_norm_on(c) && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
+  return !own_gather(c) && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
          mt_sample_lds_words(mt_sample_tbl_log2(B), sample_setsize(B)) * 4 <= kRideLdsBytes;
 }
 
@@ -902,7 +922,7 @@ static bool ride_possible(sacmi_ctx* c, int B) {
 // slots; a row a wave, every load before any store).  (The gather in L10 measured no
 // overlap: k_gemm_sample_bwd's 1024-thread workgroups fit one per CU)
 static bool ride_b_possible(sacmi_ctx* c, int B) {
-  return !obs_norm_on(c) && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM && c->bf16 && B >= 2048 &&
+  return !own_gather(c) && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM && c->bf16 && B >= 2048 &&
          mt_sample_lds_words(mt_sample_tbl_log2(B, true), sample_setsize(B)) * 4 <=
              (size_t)kDw16LdsBytes;
 }
@@ -932,8 +952,14 @@ static void enqueue_sample_gather(sacmi_ctx* c, int B, int parity, bool dev_idx,
   if (mark(c, ("gather" + t).c_str())) {
     GatherArgs ga = gather_args(c, B, bb, per);
     ga.tl = c->tl_cur;
-    if (obs_norm_on(c)) launch_gather_norm(ga, obs_norm_args(c), s);
-    else launch_gather(ga, s);
+    if (nstep_on(c)) {
+      const ObsNormArgs on = obs_norm_on(c) ? obs_norm_args(c) : ObsNormArgs{};
+      launch_gather_nstep(ga, nstep_args(c), obs_norm_on(c) ? &on : nullptr, s);
+    } else if (obs_norm_on(c)) {
+      launch_gather_norm(ga, obs_norm_args(c), s);
+    } else {
+      launch_gather(ga, s);
+    }
   }
 }
 
@@ -1142,8 +1168,8 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
   // every Adam step of this update but the sharded data-parallel form's own (enqueue_dp_sharded
   // steps this rank's chunks) reads and writes the whole of M, V
   if ((phase_mask & 6) && !c->dp_sharding_now) require_moments_whole(c);
-  REQUIRE(!(obs_norm_on(c) && ride_next), SACMI_ESTATE,
-          "observation normalisation is on: no gather rides along or is drawn ahead");
+  REQUIRE(!(own_gather(c) && ride_next), SACMI_ESTATE,
+          "observation normalisation or n-step returns on: no gather rides along or is drawn ahead");
   c->site_counter = 0;
   const BatchBufs bb = batch_bufs(c, parity);
   // where the next update's sampling + gather ride: L12 / L13 (placement A, batch <= ~2k,
@@ -1673,7 +1699,8 @@ static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_
                phase_mask | (grad_scale != 1.f ? 8 : 0) | (c->keep_grads ? 16 : 0) |
                    (pr.parity ? 32 : 0) | (pr.have_batch ? 64 : 0) | (pr.ride_next ? 128 : 0) |
                    (c->mb_graph ? 256 : 0) | (c->per_feedback ? 512 : 0) |
-                   (c->stats_on ? 1024 : 0) | (c->clip_on ? 2048 : 0) | (obs_norm_on(c) ? 4096 : 0),
+                   (c->stats_on ? 1024 : 0) | (c->clip_on ? 2048 : 0) | (obs_norm_on(c) ? 4096 : 0) |
+                   (nstep_on(c) ? 8192 : 0),
                use_ring ? c->ring_slots : 0,
                per_graph_len(c), reps};
   auto it = c->graphs.find(key);
@@ -2064,6 +2091,7 @@ int sacmi_device_count(int* n) {
 
 static void set_grad_clip(sacmi_ctx* c, double mc, double ma);
 static void set_obs_norm(sacmi_ctx* c, int32_t mode, double eps, double clip);
+static void set_nstep(sacmi_ctx* c, int32_t n);
 
 int sacmi_create(const sacmi_config* cfg, int device, sacmi_ctx** out) {
   return guard([&] {
@@ -2138,6 +2166,15 @@ int sacmi_create(const sacmi_config* cfg, int device, sacmi_ctx** out) {
       set_obs_norm(c.get(), 1, 1e-8, 10.0);
       CHECK_HIP(hipStreamSynchronize(c->stream));
     }
+    // SACMI_NSTEP=<n>: n-step returns on from creation (sacmi_set_nstep)
+    if (const char* ns = getenv("SACMI_NSTEP"); ns && ns[0]) {
+      char* end = nullptr;
+      const long n = std::strtol(ns, &end, 10);
+      REQUIRE(end != ns && *end == 0 && n >= 1 && n <= kNStepMax, SACMI_EVALUE,
+              "SACMI_NSTEP: expected an integer in [1, 32]");
+      set_nstep(c.get(), (int32_t)n);
+      CHECK_HIP(hipStreamSynchronize(c->stream));
+    }
     *out = c.release();
   });
 }
@@ -2176,6 +2213,7 @@ int sacmi_destroy(sacmi_ctx* c) {
     c->stats_ring.release(); c->stats_cnt.release(); c->stats_ws.release();
     c->clip_state.release(); c->clip_part.release(); c->gnorm_ring.release();
     c->on_mom.release(); c->on_vec.release(); c->on_actx.release();
+    c->ns_tab.release(); c->ep_end.release(); c->ep_stage.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);
@@ -2412,8 +2450,10 @@ static void obs_stats_chunk(sacmi_ctx* c, const float* rows, int m) {
 
 // Rows [n] of transitions into the ring (deque(maxlen) semantics), from either layout:
 // separate arrays (packed == nullptr) or packed rows [n][2S + A + 2] = s | a | r | s2 | d.
+// `end` (sacmi_push_ep): the rows' episode-end flags, or null (all 0); while n-step returns are
+// on every stored row's flag is written, by k_ep_scatter behind the chunk's k_push_rows
 static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float* r, const float* s2,
-                      const uint8_t* d, const float* packed, int64_t n) {
+                      const uint8_t* d, const float* packed, int64_t n, const uint8_t* end = nullptr) {
   REQUIRE(n >= 0, SACMI_EVALUE, "n < 0");
   if (n == 0) return;
   REQUIRE(packed || (s && a && r && s2 && d), SACMI_EVALUE, "null transition array");
@@ -2425,7 +2465,8 @@ static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float*
     // (observation statistics updating, mode 1: every row takes the chunked path below, where
     // k_obs_stats sees it; rows already pending are flushed first, uncounted: they were pushed
     // before the mode was set)
-    if (c->mb_host && !c->inflight && c->on_mode != 1 && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
+    // (n-step returns on: likewise — the mailbox scatter carries no flags)
+    if (c->mb_host && !c->inflight && c->on_mode != 1 && !nstep_on(c) && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
         c->mb_pending + n <= sacmi_ctx::kMbRows && c->mb_pending + n <= c->capacity) {
       // (rows pending beyond the capacity would map two rows onto one ring slot in the
       // sampler's scatter, stored in no fixed order: the chunked path's `skip` handles that)
@@ -2505,8 +2546,16 @@ static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float*
       std::memcpy(h + m * (S + A + 1), s2 + i * S, (size_t)m * S * 4);
       for (int64_t j = 0; j < m; ++j) hd[j] = d[i + j] ? 1.f : 0.f;
     }
+    // the chunk's flags in staging of their own beside slot k: the slot's wait above covers
+    // them (push_zc_epoch / push_ev, recorded behind both copies)
+    uint8_t* he = nullptr;
+    if (nstep_on(c)) {
+      he = zc ? c->ep_zc_host[k] : c->ep_host[k];
+      for (int64_t j = 0; j < m; ++j) he[j] = end && end[i + j] ? 1 : 0;
+    }
     if (!zc) {
       CHECK_HIP(hipMemcpyAsync(c->stage.p, h, (size_t)m * rowf * 4, hipMemcpyHostToDevice, c->stream));
+      if (he) CHECK_HIP(hipMemcpyAsync(c->ep_stage.p, he, (size_t)m, hipMemcpyHostToDevice, c->stream));
       CHECK_HIP(hipEventRecord(c->push_ev[k], c->stream));
     }
     const int64_t done_rows = i + m - skip;
@@ -2526,6 +2575,7 @@ static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float*
     // scatter: the slot's reuse waits for this stream (push_zc_epoch / the copy's event, and
     // the next copy into `stage` is stream-ordered behind this reader)
     if (c->on_mode == 1) obs_stats_chunk(c, pa.stage, (int)m);
+    if (he) launch_ep_scatter(zc ? c->ep_zc_dev[k] : c->ep_stage.p, c->ep_end.p, m, pa.pos0, cap, c->stream);
   }
   const int64_t added = n - skip;
   if (c->cfg.replay_kind == SACMI_REPLAY_PER) {
@@ -2544,6 +2594,21 @@ int sacmi_push(sacmi_ctx* c, const float* s, const float* a, const float* r, con
 int sacmi_push_packed(sacmi_ctx* c, const float* rows, int64_t n) {
   return guard([&] {
     pf_touch(c); push_impl(c, nullptr, nullptr, nullptr, nullptr, nullptr, rows, n); });
+}
+
+int sacmi_push_ep(sacmi_ctx* c, const float* s, const float* a, const float* r, const float* s2,
+                  const uint8_t* d, const uint8_t* end, int64_t n) {
+  return guard([&] {
+    REQUIRE(c, SACMI_EVALUE, "null ctx");
+    REQUIRE(nstep_on(c), SACMI_ESTATE, "n-step returns are off: no episode-end flags are kept");
+    pf_touch(c); push_impl(c, s, a, r, s2, d, nullptr, n, end); });
+}
+
+int sacmi_push_packed_ep(sacmi_ctx* c, const float* rows, const uint8_t* end, int64_t n) {
+  return guard([&] {
+    REQUIRE(c, SACMI_EVALUE, "null ctx");
+    REQUIRE(nstep_on(c), SACMI_ESTATE, "n-step returns are off: no episode-end flags are kept");
+    pf_touch(c); push_impl(c, nullptr, nullptr, nullptr, nullptr, nullptr, rows, n, end); });
 }
 
 int sacmi_len(sacmi_ctx* c, int64_t* n) {
@@ -3052,6 +3117,107 @@ int sacmi_obs_norm_get_vectors(sacmi_ctx* c, float* nmean, float* nrstd, int32_t
   });
 }
 
+// ---------------------------------------------------------------------------
+// n-step returns in the gather (nstep.hip)
+static void nstep_alloc(sacmi_ctx* c) {
+  if (c->ep_end.p) return;
+  c->ns_tab.alloc((size_t)kNStepMax + 4);
+  c->ep_end.alloc((size_t)c->capacity);
+  c->ep_stage.alloc((size_t)c->push_rows);
+  for (int i = 0; i < sacmi_ctx::kPushSlots; ++i) {
+    CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->ep_host[i]), (size_t)c->push_rows,
+                            hipHostMallocDefault));
+    CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->ep_zc_host[i]), sacmi_ctx::kPushZcRows,
+                            hipHostMallocMapped | hipHostMallocCoherent));
+    CHECK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->ep_zc_dev[i]), c->ep_zc_host[i], 0));
+  }
+}
+
+static void set_nstep(sacmi_ctx* c, int32_t n) {
+  REQUIRE(c, SACMI_EVALUE, "null ctx");
+  REQUIRE(n >= 1 && n <= kNStepMax, SACMI_EVALUE, "n must be in [1, 32] (1: off)");
+  static_assert(sacmi_ctx::kPushSlots == 2, "ep_host / ep_zc_host hold one entry per push slot");
+  pf_touch(c);
+  mb_flush(c);      // (rows pushed while off reach the ring through the mailbox's scatter)
+  const bool was_on = nstep_on(c);
+  c->nstep = n;     // (on / off is part of the graph key; the value is device state)
+  if (n == 1) return;
+  nstep_alloc(c);
+  // off -> on: no row stored so far carries a flag
+  if (!was_on) CHECK_HIP(hipMemsetAsync(c->ep_end.p, 0, (size_t)c->capacity, c->stream));
+  // stream-ordered, the table by value: updates already enqueued keep the n they were enqueued under
+  NStepTable tab{};
+  for (int j = 0; j < kNStepMax; ++j) tab.g[j] = (float)std::pow((double)c->cfg.gamma, (double)j);
+  tab.n = n;
+  launch_nstep_table(tab, c->ns_tab.p, reinterpret_cast<int32_t*>(c->ns_tab.p + kNStepMax), c->stream);
+}
+
+int sacmi_set_nstep(sacmi_ctx* c, int32_t n) {
+  return guard([&] { set_nstep(c, n); });
+}
+
+int sacmi_nstep(sacmi_ctx* c, int32_t* n) {
+  return guard([&] {
+    REQUIRE(c && n, SACMI_EVALUE, "null argument");
+    *n = c->nstep;
+  });
+}
+
+int sacmi_mark_episode_end(sacmi_ctx* c) {
+  return guard([&] {
+    REQUIRE(c, SACMI_EVALUE, "null ctx");
+    REQUIRE(nstep_on(c), SACMI_ESTATE, "n-step returns are off: no episode-end flags are kept");
+    REQUIRE(c->len > 0, SACMI_ESTATE, "the replay is empty");
+    pf_touch(c);
+    mb_flush(c);
+    const int64_t newest = (c->wpos - 1 + c->capacity) % c->capacity;
+    CHECK_HIP(hipMemsetAsync(c->ep_end.p + newest, 1, 1, c->stream));
+  });
+}
+
+int sacmi_get_episode_ends(sacmi_ctx* c, const int64_t* idx, int64_t n, int32_t by_slot, uint8_t* out) {
+  return guard([&] {
+    REQUIRE(c && (n == 0 || (idx && out)), SACMI_EVALUE, "null argument");
+    REQUIRE(n >= 0, SACMI_EVALUE, "n < 0");
+    pf_touch(c);
+    mb_flush(c);
+    const int64_t head = c->len < c->capacity ? 0 : c->wpos;
+    for (int64_t i = 0; i < n; ++i)
+      REQUIRE(idx[i] >= 0 && idx[i] < c->len, SACMI_EVALUE, by_slot ? "slot out of range" : "index out of range");
+    if (n == 0) return;
+    std::vector<uint8_t> h((size_t)c->capacity, 0);     // (never switched on: no flags)
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    if (c->ep_end.p && nstep_on(c))
+      CHECK_HIP(hipMemcpy(h.data(), c->ep_end.p, (size_t)c->capacity, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i)
+      out[i] = h[(size_t)(by_slot ? idx[i] : (head + idx[i]) % c->capacity)];
+  });
+}
+
+int sacmi_read_batch_rd(sacmi_ctx* c, int32_t batch, float* r, float* d) {
+  return guard([&] {
+    REQUIRE(c && r && d, SACMI_EVALUE, "null argument");
+    REQUIRE(batch >= 1 && batch <= c->Bm, SACMI_EVALUE, "bad batch");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    CHECK_HIP(hipMemcpy(r, c->r.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(d, c->d.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int sacmi_debug_set_done(sacmi_ctx* c, const int64_t* slots, const float* values, int64_t n) {
+  return guard([&] {
+    REQUIRE(c && (n == 0 || (slots && values)), SACMI_EVALUE, "null argument");
+    REQUIRE(n >= 0, SACMI_EVALUE, "n < 0");
+    for (int64_t i = 0; i < n; ++i)
+      REQUIRE(slots[i] >= 0 && slots[i] < c->capacity, SACMI_EVALUE, "slot out of range");
+    pf_touch(c);
+    mb_flush(c);
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n; ++i)
+      CHECK_HIP(hipMemcpy(c->done.p + slots[i], values + i, 4, hipMemcpyHostToDevice));
+  });
+}
+
 int sacmi_step_phase(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_scale) {
   return guard([&] {
     refuse_obs_norm(c);
@@ -3071,6 +3237,7 @@ int sacmi_step_phase_ex(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_s
     refuse_feedback(c);
     REQUIRE(phase >= 0 && phase <= 3, SACMI_EVALUE, "phase must be 0, 1, 2 or 3");
     REQUIRE(parity == 0 || parity == 1, SACMI_EVALUE, "parity must be 0 or 1");
+    REQUIRE(!(nstep_on(c) && ride_next), SACMI_ESTATE, "n-step returns are on: no gather rides along");
     if (phase == 0 || phase == 3) check_device_batch(c, batch);
     PhaseRide pr;
     pr.parity = parity;

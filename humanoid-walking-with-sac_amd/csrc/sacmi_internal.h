@@ -674,6 +674,26 @@ void launch_obs_normalize(const float* src, int lds, float* dst, int ldd, int n,
                           const ObsNormArgs& on, hipStream_t s);
 void launch_gather_norm(const GatherArgs& a, const ObsNormArgs& on, hipStream_t s);
 
+// N-step returns in the gather (nstep.hip; sacmi_set_nstep).  Device state, one per context,
+// allocated when first switched on: the table g[j] = (float)(gamma ** j), j < kNStepMax, and the
+// steps n behind it (one buffer, written stream-ordered by k_nstep_table), and the ring's
+// per-slot episode-end flags ep_end [capacity].  The gather's view is an argument block of its
+// own, as ObsNormArgs: GatherArgs, RideAlong and GemmBatch keep their bytes
+constexpr int kNStepMax = 32;
+struct NStepArgs {
+  const int32_t* n;        // steps, 2..kNStepMax while on; read on the device: changing it
+                           //   re-captures nothing
+  const float* g;          // [kNStepMax]
+  const uint8_t* ep_end;   // [capacity]
+};
+struct NStepTable { float g[kNStepMax]; int32_t n; };
+void launch_nstep_table(const NStepTable& tab, float* g, int32_t* n, hipStream_t s);
+// on: null, or the normalising form's vectors (k_gather_nstep<true>)
+void launch_gather_nstep(const GatherArgs& a, const NStepArgs& ns, const ObsNormArgs* on, hipStream_t s);
+// ep_end[(pos0 + i) % cap] = stage[i] != 0 for i < n (stage: device or host-mapped memory)
+void launch_ep_scatter(const uint8_t* stage, uint8_t* ep_end, int64_t n, int64_t pos0, int64_t cap,
+                       hipStream_t s);
+
 // Rows sacmi_push left in host-mapped staging for the next synchronous update (the
 // trainer's row per env step): that update's sampler kernel scatters them into the ring
 // before it draws, instead of a scatter launch of their own ahead of the update

@@ -104,6 +104,14 @@ _PROTOS = {
     "sacmi_obs_norm_get_moments": [c_vp, c_f64p, c_f64p, c_f64p, ctypes.c_int32],
     "sacmi_obs_norm_set_moments": [c_vp, ctypes.c_double, c_f64p, c_f64p, ctypes.c_int32],
     "sacmi_obs_norm_get_vectors": [c_vp, c_f32p, c_f32p, ctypes.c_int32],
+    "sacmi_set_nstep": [c_vp, ctypes.c_int32],
+    "sacmi_nstep": [c_vp, c_i32p],
+    "sacmi_push_ep": [c_vp, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_u8p, ctypes.c_int64],
+    "sacmi_push_packed_ep": [c_vp, c_vp, c_u8p, ctypes.c_int64],
+    "sacmi_mark_episode_end": [c_vp],
+    "sacmi_get_episode_ends": [c_vp, c_i64p, ctypes.c_int64, ctypes.c_int32, c_u8p],
+    "sacmi_read_batch_rd": [c_vp, ctypes.c_int32, c_f32p, c_f32p],
+    "sacmi_debug_set_done": [c_vp, c_i64p, c_f32p, ctypes.c_int64],
     "sacmi_step_phase": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_float],
     "sacmi_grad_buffer": [c_vp, ctypes.c_int, ctypes.POINTER(c_vp), c_i64p],
     "sacmi_grad_arena_numel": [c_vp, c_i64p],

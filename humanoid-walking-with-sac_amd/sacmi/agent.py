@@ -132,8 +132,16 @@ class SAC:
                  prioritized_replay: bool = False, per_alpha: float = 0.6,
                  per_beta_start: float = 0.4, per_beta_frames: int = 100000,
                  diagnostics: bool = False, max_grad_norm=None,
-                 normalize_obs: bool = False, obs_clip: float = 10.0, obs_norm_eps: float = 1e-8):
-        """``normalize_obs``: running observation normalisation on the device.  The replay keeps
+                 normalize_obs: bool = False, obs_clip: float = 10.0, obs_norm_eps: float = 1e-8,
+                 n_step: int = 1):
+        """``n_step``: multi-step returns, 1..32 (1: the reference's one-step target).  Every
+        sampled row's target becomes r_0 + gamma r_1 + ... + gamma^m r_m + gamma^(m+1) (min Q -
+        alpha log pi)(s'_m), the chain of stored rows cut at a terminal, at an episode end
+        (``replay_buffer.push(..., episode_end=True)`` or ``replay_buffer.mark_episode_end()``
+        for ends that are not terminals, e.g. a step-limit cut), at the newest row, or after
+        ``n_step`` rows.  Made in the update's gather from the replay as it is then; checkpoints
+        carry ``n_step`` and the episode-end flags.
+        ``normalize_obs``: running observation normalisation on the device.  The replay keeps
         raw observations; every update's minibatch (state and next state) and every
         ``select_action`` state pass through ``clamp((x - mean) / sqrt(var + obs_norm_eps),
         -obs_clip, obs_clip)`` with the running mean and population variance of the states
@@ -165,6 +173,8 @@ class SAC:
         operands with fp32 accumulation, fp32 master weights / Adam / losses)."""
         if networks not in MODELS:
             raise ValueError(f"networks must be one of {sorted(MODELS)}")
+        if int(n_step) != n_step or not 1 <= int(n_step) <= 32:
+            raise ValueError("n_step must be an integer in [1, 32]")
         QNetwork, GaussianPolicy = MODELS[networks]
         self.gamma = gamma
         self.tau = tau
@@ -220,9 +230,15 @@ class SAC:
             self._ctx.set_grad_clip(float(mc), float(ma))
         if normalize_obs:
             self._ctx.set_obs_norm(1, float(obs_norm_eps), float(obs_clip))
+        if int(n_step) > 1:
+            self._ctx.set_nstep(int(n_step))
         st = random.getstate()             # device sampling stream starts at `random`'s
         self._ctx.set_mt(0, np.array(st[1][:624], np.uint32), st[1][624])
         self._mt_adopted = st[1]           # (the Python stream state the device holds)
+
+    @property
+    def n_step(self) -> int:
+        return self._ctx.nstep()
 
     # -- mirrored attributes ---------------------------------------------------------
     def _flush_device(self):
@@ -467,7 +483,9 @@ class SAC:
             ck["replay_buffer"] = {"state": torch.from_numpy(s), "action": torch.from_numpy(a),
                                    "reward": torch.from_numpy(r),
                                    "next_state": torch.from_numpy(s2),
-                                   "done": torch.from_numpy(d)}
+                                   "done": torch.from_numpy(d),
+                                   "episode_end": torch.from_numpy(self.replay_buffer.episode_ends())}
+        ck["n_step"] = self.n_step
         on = self._obs_norm_entry()
         if on is not None:
             ck["obs_norm"] = on
@@ -480,9 +498,18 @@ class SAC:
         # the replay rows are checked before anything is overwritten (a checkpoint whose rows
         # do not fit this agent leaves it untouched), and replace the buffer at the end, as
         # the reference's assignment does (sac_imp.py:229-230)
-        rows = None
+        rows = ends = None
         if load_replay_buffer and "replay_buffer" in ck:
             rows = self._checkpoint_rows(ck["replay_buffer"])
+            rb = ck["replay_buffer"]
+            if isinstance(rb, dict) and "episode_end" in rb:
+                ends = np.asarray(rb["episode_end"].numpy() if torch.is_tensor(rb["episode_end"])
+                                  else rb["episode_end"]).astype(bool).reshape(-1)
+                if ends.size != len(rows[2]):
+                    raise ValueError("checkpoint episode_end flags do not match its replay rows")
+        n_step = int(ck.get("n_step", self.n_step))
+        if not 1 <= n_step <= 32:
+            raise ValueError("checkpoint n_step must be in [1, 32]")
         self._load_nets(ck)
         for name in ("policy", "q1", "q2"):
             key = f"{name}_optimizer_state_dict"
@@ -494,13 +521,15 @@ class SAC:
         if "alpha_optimizer_state_dict" in ck and self.automatic_entropy_tuning:
             self.alpha_optimizer.load_state_dict(ck["alpha_optimizer_state_dict"])
         self._load_obs_norm(ck)
+        if n_step != self.n_step:
+            self._ctx.set_nstep(n_step)
         if rows is not None:
             # the checkpoint's statistics already count these rows: frozen around the reload
             mode, eps, clip = self._ctx.obs_norm()
             if mode == 1:
                 self._ctx.set_obs_norm(2, eps, clip)
             try:
-                self.replay_buffer._replace_arrays(*rows)
+                self.replay_buffer._replace_arrays(*rows, episode_end=ends)
             finally:
                 if mode == 1:
                     self._ctx.set_obs_norm(1, eps, clip)

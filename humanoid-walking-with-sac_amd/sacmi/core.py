@@ -153,7 +153,9 @@ class Context:
         L.call("sacmi_rng_seed_device", self._h, int(seed), int(offset))
 
     # -- replay --------------------------------------------------------------------
-    def push(self, s, a, r, s2, d) -> None:
+    def push(self, s, a, r, s2, d, episode_end=None) -> None:
+        """``episode_end`` (bool per row, n-step returns on only): the rows' episode-end flags
+        (sacmi.h sacmi_push_ep)."""
         S, A = self.cfg.state_dim, self.cfg.action_dim
         s = np.ascontiguousarray(s, np.float32).reshape(-1, S)
         n = s.shape[0]
@@ -161,14 +163,70 @@ class Context:
         r = np.ascontiguousarray(r, np.float32).reshape(n)
         s2 = np.ascontiguousarray(s2, np.float32).reshape(n, S)
         d = np.ascontiguousarray(np.asarray(d).astype(bool), np.uint8).reshape(n)
-        L.call("sacmi_push", self._h, L.fptr(s), L.fptr(a), L.fptr(r), L.fptr(s2), L.u8ptr(d), n)
+        if episode_end is None:
+            L.call("sacmi_push", self._h, L.fptr(s), L.fptr(a), L.fptr(r), L.fptr(s2), L.u8ptr(d), n)
+            return
+        e = np.ascontiguousarray(np.asarray(episode_end).astype(bool), np.uint8).reshape(n)
+        L.call("sacmi_push_ep", self._h, L.fptr(s), L.fptr(a), L.fptr(r), L.fptr(s2), L.u8ptr(d),
+               L.u8ptr(e), n)
 
-    def push_packed(self, rows: np.ndarray, n: int) -> None:
-        """n packed rows (float32 [>= n][2S + A + 2]: s | a | r | s2 | d), copy-in."""
+    def push_packed(self, rows: np.ndarray, n: int, episode_end=None) -> None:
+        """n packed rows (float32 [>= n][2S + A + 2]: s | a | r | s2 | d), copy-in;
+        ``episode_end``: as ``push``."""
         S, A = self.cfg.state_dim, self.cfg.action_dim
         assert rows.dtype == np.float32 and rows.flags.c_contiguous and rows.shape[-1] == 2 * S + A + 2
         assert rows.size >= n * (2 * S + A + 2)
-        L.call("sacmi_push_packed", self._h, rows.ctypes.data, int(n))
+        if episode_end is None:
+            L.call("sacmi_push_packed", self._h, rows.ctypes.data, int(n))
+            return
+        e = np.ascontiguousarray(np.asarray(episode_end).astype(bool), np.uint8).reshape(-1)
+        assert e.size >= n
+        L.call("sacmi_push_packed_ep", self._h, rows.ctypes.data, L.u8ptr(e), int(n))
+
+    # -- n-step returns (sacmi.h sacmi_set_nstep) ------------------------------------
+    def set_nstep(self, n: int) -> None:
+        """N-step returns made in the update's gather from the ring as it is at sample time;
+        ``n`` in 1..32, 1: off."""
+        L.call("sacmi_set_nstep", self._h, int(n))
+        self._nstep = int(n)
+
+    def nstep(self) -> int:
+        """The steps in effect (1: off).  Mirrored on the host: the drop-in buffers ask at every
+        flush, i.e. once per env step in a trainer loop."""
+        n = getattr(self, "_nstep", None)
+        if n is None:                       # (SACMI_NSTEP may have set it at creation)
+            v = ctypes.c_int32()
+            L.call("sacmi_nstep", self._h, ctypes.byref(v))
+            n = self._nstep = int(v.value)
+        return n
+
+    def mark_episode_end(self) -> None:
+        """Flag the newest stored row as its episode's last (e.g. a step-limit cut)."""
+        L.call("sacmi_mark_episode_end", self._h)
+
+    def get_episode_ends(self, idx, by_slot: bool = False) -> np.ndarray:
+        """The episode-end flags (bool) of deque positions ``idx`` (ring slots with
+        ``by_slot``); all False while n-step returns are off.  Synchronises."""
+        idx = np.ascontiguousarray(idx, np.int64).reshape(-1)
+        out = np.zeros(idx.size, np.uint8)
+        L.call("sacmi_get_episode_ends", self._h, L.i64ptr(idx), idx.size, 1 if by_slot else 0,
+               L.u8ptr(out))
+        return out.astype(bool)
+
+    def read_batch_rd(self, batch: int):
+        """Test hook: (r[batch], d[batch]) float32 of batch set 0 as the last update's gather left
+        them (the indices: ``read_batch``)."""
+        r, d = np.zeros(batch, np.float32), np.zeros(batch, np.float32)
+        L.call("sacmi_read_batch_rd", self._h, int(batch), L.fptr(r), L.fptr(d))
+        return r, d
+
+    def debug_set_done(self, slots, values) -> None:
+        """Test hook: raw float32 ``values`` into the ring's done array at ring ``slots``."""
+        slots = np.ascontiguousarray(slots, np.int64).reshape(-1)
+        values = np.ascontiguousarray(values, np.float32).reshape(-1)
+        if slots.size != values.size:
+            raise ValueError("slots and values differ in length")
+        L.call("sacmi_debug_set_done", self._h, L.i64ptr(slots), L.fptr(values), slots.size)
 
     def __len__(self) -> int:
         n = ctypes.c_int64()

@@ -33,6 +33,7 @@ class _Staged:
         self._ctx = ctx
         self._replay = replay
         self._rows = []            # pending (s, a, r, s2, d)
+        self._ends = []            # their episode-end flags (n-step returns)
         self._pack = None          # packed staging for sacmi_push_packed
 
     # -- device binding ------------------------------------------------------------
@@ -51,6 +52,9 @@ class _Staged:
         if not self._rows:
             return
         ctx = self._ctx
+        nstep = ctx.nstep() >= 2
+        if not nstep and any(self._ends):
+            raise ValueError("episode_end needs n-step returns on (Context.set_nstep / SAC(n_step=))")
         S, A = ctx.cfg.state_dim, ctx.cfg.action_dim
         n = len(self._rows)
         # packed rows s | a | r | s2 | d in a reused buffer (sacmi_push_packed)
@@ -65,13 +69,29 @@ class _Staged:
             p[i, S + A + 1:w - 1] = np.asarray(s2i, np.float32).reshape(S)
             p[i, w - 1] = 1.0 if di else 0.0
         self._rows.clear()
-        ctx.push_packed(p, n)
+        ends, self._ends = self._ends, []
+        if nstep:
+            ctx.push_packed(p, n, episode_end=np.asarray(ends, bool))
+        else:
+            ctx.push_packed(p, n)
 
-    def push(self, state, action, reward, next_state, done):
+    def push(self, state, action, reward, next_state, done, episode_end=False):
+        """``episode_end``: this row is its episode's last although ``done`` is False (a
+        step-limit cut); kept with the row, used by the n-step gather (Context.set_nstep)."""
         self._ensure_ctx(state, action)
         self._rows.append((state, action, reward, next_state, done))
+        self._ends.append(bool(episode_end))
         if len(self._rows) >= _STAGE:
             self._flush()
+
+    def mark_episode_end(self):
+        """Flag the last pushed row as its episode's last."""
+        if self._ends:
+            self._ends[-1] = True
+        elif self._ctx is not None:
+            self._ctx.mark_episode_end()
+        else:
+            raise ValueError("the replay is empty")
 
     def __len__(self):
         if self._ctx is None:
@@ -100,6 +120,7 @@ class _Staged:
         (a deque(maxlen) keeps the last `capacity` of them)."""
         rows = list(rows)
         self._rows.clear()
+        self._ends.clear()
         if self._ctx is None:
             if not rows:
                 return
@@ -109,9 +130,10 @@ class _Staged:
             self.push(*row)
         self._flush()
 
-    def _replace_arrays(self, s, a, r, s2, d):
+    def _replace_arrays(self, s, a, r, s2, d, episode_end=None):
         """Replace the contents with the rows of stacked arrays (the drop-in's checkpoint form)."""
         self._rows.clear()
+        self._ends.clear()
         if len(s) == 0:
             # an empty replay (the reference assigns an empty buffer): nothing to push, and
             # no context to create from rows that do not exist
@@ -120,7 +142,18 @@ class _Staged:
             return
         self._ensure_ctx(s[0], a[0])
         self._ctx.replay_clear()
-        self._ctx.push(s, a, r, s2, d)
+        if episode_end is not None and self._ctx.nstep() >= 2:
+            self._ctx.push(s, a, r, s2, d, episode_end=episode_end)
+        else:
+            self._ctx.push(s, a, r, s2, d)
+
+    def episode_ends(self) -> np.ndarray:
+        """The stored rows' episode-end flags, oldest first (all False while n-step is off)."""
+        self._flush()
+        n = len(self)
+        if n == 0:
+            return np.zeros(0, bool)
+        return self._ctx.get_episode_ends(np.arange(n))
 
 
 class ReplayBuffer(_Staged):

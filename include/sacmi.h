@@ -355,6 +355,65 @@ int sacmi_obs_norm_set_moments(sacmi_ctx* ctx, double count, const double* mean,
 /* nmean, nrstd [S] f32 as the gather reads them (synchronises) */
 int sacmi_obs_norm_get_vectors(sacmi_ctx* ctx, float* nmean, float* nrstd, int32_t S);
 
+/* ---- n-step returns in the replay gather ------------------------------------------------ */
+/* Multi-step targets, made where the minibatch is gathered, from the ring as it is at sample
+ * time: nothing is stored per row, pushes are not delayed, and the return follows the ring's
+ * current contents.  The reference bootstraps one step ahead (sac_imp.py:86-93).
+ *
+ * n = steps, 1 <= n <= 32 (else SACMI_EVALUE); n = 1 is off (default; the update's launches are
+ * exactly those of a context that never called this).  g[j] = (float)(gamma ** j), j = 0..31,
+ * computed on the host in fp64 and rounded once (g[0] = 1).
+ *
+ * For a sampled row at deque position i (prioritized contexts: ring slot p0, i = (p0 - head +
+ * capacity) % capacity) the chain is p_j = (p0 + j) % capacity, j = 0, 1, ...  Row p_j stops it
+ * if done[p_j] != 0, or its episode-end flag is set (below), or j == min(n - 1, len - 1 - i):
+ * the chain never passes the newest row, so it never wraps onto the oldest.  m = the smallest
+ * stopping j.  Then, in fp32 with every operation rounded on its own (no contraction),
+ *     R  = r_0;  for j = 1..m in that order:  R = R + g[j] * r_j
+ *     d' = done[p_m] != 0 ? 1 : (m == 0 ? 0 : 1 - g[m])
+ * and the gathered row is s, a from p0, r[b] = R, s2 from p_m, d[b] = d'.  A row with m == 0
+ * is bit for bit the one-step row.  A chain ended by a flag with done == 0 bootstraps from that
+ * row's s2 (a time-limit truncation).  A NaN reward propagates into R as it would into r.
+ *
+ * Nothing downstream of the gather changes: the row algebra computes fl(fl(1 - d') * gamma) *
+ * min(q1t, q2t) as before, which DEFINES the effective bootstrap coefficient.  For g[m] >= 0.5
+ * both subtractions are exact and it is fl(g[m] * (float)gamma); below that it is within about
+ * 2 ulp of gamma^(m+1) (documented, not a defect).  The diagnostics and the prioritized
+ * feedback's TD errors are then the n-step ones.
+ *
+ * Episode boundaries: the ring keeps one flag byte per slot.  While n >= 2 EVERY stored row
+ * writes its flag, 0 or 1 (sacmi_push / sacmi_push_packed write 0), so an evicted row's flag is
+ * overwritten with its slot; switching on from off clears all flags (stream-ordered).
+ * sacmi_push_ep / sacmi_push_packed_ep are sacmi_push / sacmi_push_packed with end: [n] u8 or
+ * NULL (all 0); sacmi_mark_episode_end sets the flag of the newest stored row (a trainer that
+ * learns of a time-limit cut only after the push).  All three return SACMI_ESTATE while off;
+ * sacmi_mark_episode_end also with an empty replay.  A terminal row needs no flag.
+ *
+ * On / off selects another captured graph; the value of n and the table are stream-ordered
+ * device state: changing n among values >= 2 re-captures nothing.  On, the minibatch is
+ * gathered by a launch of its own in every update (k_gather_nstep): no gather rides along and no
+ * batch is drawn ahead (sacmi_step_ride_possible reports 0; sacmi_step_phase_ex with ride_next
+ * returns SACMI_ESTATE), and every pushed row takes the chunked device path (the push mailbox is
+ * bypassed).  The phase-split and data-parallel updates stay allowed: the chain is local to a
+ * rank's own ring.  Composes with observation normalisation (s from p0 and s2 from p_m are
+ * normalised), staged indices, prioritized replay and its feedback mode.
+ *
+ * SACMI_NSTEP=<n> in the environment at sacmi_create switches it on from the start.
+ * Additive: the ABI version is unchanged. */
+int sacmi_set_nstep(sacmi_ctx* ctx, int32_t n);
+int sacmi_nstep(sacmi_ctx* ctx, int32_t* n);
+int sacmi_push_ep(sacmi_ctx* ctx, const float* s, const float* a, const float* r,
+                  const float* s2, const uint8_t* d, const uint8_t* end, int64_t n);
+int sacmi_push_packed_ep(sacmi_ctx* ctx, const float* rows, const uint8_t* end, int64_t n);
+int sacmi_mark_episode_end(sacmi_ctx* ctx);
+/* The flags of rows idx[n] (deque positions, or ring slots with by_slot), for checkpoints;
+ * all 0 while off.  Synchronises. */
+int sacmi_get_episode_ends(sacmi_ctx* ctx, const int64_t* idx, int64_t n, int32_t by_slot, uint8_t* out);
+/* Test hooks: r[batch], d[batch] of minibatch set 0 as the last update's gather left them (as
+ * sacmi_read_batch); raw fp32 values into the ring's done array at ring slots. */
+int sacmi_read_batch_rd(sacmi_ctx* ctx, int32_t batch, float* r, float* d);
+int sacmi_debug_set_done(sacmi_ctx* ctx, const int64_t* slots, const float* values, int64_t n);
+
 /* Data-parallel split of the step (one process per GPU).  phase 0: sample, gather,
  * forward, critic backward -> critic gradient buffer; phase 1: critic Adam + Polyak,
  * actor forward/backward -> actor gradient buffer; phase 2: actor Adam + alpha;
