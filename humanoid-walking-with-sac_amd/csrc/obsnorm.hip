@@ -13,6 +13,7 @@
 //
 // Vectors: nmean[k] = (float)mean, nrstd[k] = (float)(1 / sqrt(M2 / count + eps)) in fp64,
 // rounded once; count == 0: mean 0, rstd 1 (identity), as the pad columns up to Sp.
+#include "moments_dev.h"
 #include "replay_dev.h"
 
 namespace sacmi {
@@ -21,26 +22,6 @@ namespace {
 
 constexpr int kObsThreads = kObsCols * kObsRowLanes;
 static_assert(kObsThreads % kWave == 0, "whole waves");
-
-struct Moments { double n, mean, m2; };
-
-// a <- a merged with b (Chan et al.): exact hand-over when either side is empty
-__device__ __forceinline__ void chan_merge(Moments& a, const Moments& b) {
-  if (b.n == 0.0) return;
-  if (a.n == 0.0) { a = b; return; }
-  const double n = a.n + b.n, d = b.mean - a.mean;
-  a.mean = a.mean + d * (b.n / n);
-  a.m2 = a.m2 + b.m2 + d * d * (a.n * b.n / n);
-  a.n = n;
-}
-
-__device__ __forceinline__ void welford_step(Moments& a, float xf) {
-  const double x = (double)xf;
-  a.n += 1.0;
-  const double d = x - a.mean;
-  a.mean += d / a.n;
-  a.m2 += d * (x - a.mean);
-}
 
 __device__ __forceinline__ void obs_vectors(double n, double mean, double m2, double eps,
                                             float* nmean, float* nrstd) {

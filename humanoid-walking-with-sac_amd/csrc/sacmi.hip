@@ -306,6 +306,14 @@ struct sacmi_ctx {
   uint8_t* ep_host[2] = {};
   uint8_t* ep_zc_host[2] = {};
   uint8_t* ep_zc_dev[2] = {};
+  // sacmi_set_reward_norm (retnorm.hip): the mode (0 off, 1 running, 2 frozen, 3 constant scale),
+  // the settings, the state rn_state [count | mean | M2 | ret] fp64, the words the per-update
+  // kernel reads rn_kc [k | clip], and the normalised reward of either batch set; allocated when
+  // first needed
+  int rn_mode = 0;
+  double rn_scale = 1.0, rn_eps = 1e-8, rn_clip = 10.0;
+  sacmi::DevBuf<double> rn_state;
+  sacmi::DevBuf<float> rn_kc, rn, rnb;
   std::map<sacmi::GraphKey, hipGraphExec_t> graphs;
   bool use_graphs = true;
   bool G_external = false;
@@ -842,13 +850,14 @@ static PerArgs per_args_impl(sacmi_ctx* c, int k, int gen_u, int32_t* idx32, int
 struct BatchBufs {
   int32_t* idx32; int64_t* idx64; float* xq; float* x2; float* r; float* d;
   float* w; float* td; float* pv;   // (null on a uniform context)
+  float* rn;                        // r normalised (sacmi_set_reward_norm; null until first on)
 };
 static BatchBufs batch_bufs(sacmi_ctx* c, int parity) {
   if (parity == 0)
     return BatchBufs{c->idx32.p, c->idx64.p, c->xq.p, c->x2.p, c->r.p, c->d.p,
-                     c->per_w.p, c->per_td.p, c->per_pv.p};
+                     c->per_w.p, c->per_td.p, c->per_pv.p, c->rn.p};
   return BatchBufs{c->idx32b.p, c->idx64b.p, c->xqb.p, c->x2b.p, c->rb.p, c->db.p,
-                   c->per_wb.p, c->per_tdb.p, c->per_pvb.p};
+                   c->per_wb.p, c->per_tdb.p, c->per_pvb.p, c->rnb.p};
 }
 // the prioritized sampler writes the indices of batch set bb (set 0 by default)
 static PerArgs per_args(sacmi_ctx* c, int k, int gen_u, const BatchBufs* bb) {
@@ -904,8 +913,18 @@ static ObsNormArgs obs_norm_args(const sacmi_ctx* c) {
 
 // N-step returns on: as above — NStepArgs is a kernel parameter of the gather's own
 static bool nstep_on(const sacmi_ctx* c) { return c->nstep >= 2; }
+// the episode-end flags of a push are accepted: they cut the n-step chains, or reset the running
+// return (reward normalisation running or frozen)
+static bool ep_flags_on(const sacmi_ctx* c) { return nstep_on(c) || c->rn_mode == 1 || c->rn_mode == 2; }
 static NStepArgs nstep_args(const sacmi_ctx* c) {
   return NStepArgs{reinterpret_cast<const int32_t*>(c->ns_tab.p + kNStepMax), c->ns_tab.p, c->ep_end.p};
+}
+// Reward normalisation on: one small launch of its own behind whatever produced the minibatch
+// (k_reward_norm); the gathers, the rides and the draw-ahead are as they are without it
+static bool reward_norm_on(const sacmi_ctx* c) { return c->rn_mode != 0; }
+// the reward the update's readers take (the L5 row prologue, the diagnostics)
+static const float* batch_reward(const sacmi_ctx* c, const BatchBufs& bb) {
+  return reward_norm_on(c) ? bb.rn : bb.r;
 }
 // the update launches a gather of its own: none rides, none is drawn ahead
 static bool own_gather(const sacmi_ctx* c) { return obs_norm_on(c) || nstep_on(c); }
@@ -1062,7 +1081,7 @@ static void enqueue_stats(sacmi_ctx* c, int B, const BatchBufs& bb, hipStream_t 
   if (!mark(c, "update_stats")) return;
   StatsArgs a{};
   a.dotp = c->dotp.p; a.nparts = c->nparts; a.B = B; a.logp = c->logp.p;
-  a.r = bb.r; a.d = bb.d; a.sc = c->sc.p; a.log_alpha = c->P.p + c->la_idx;
+  a.r = batch_reward(c, bb); a.d = bb.d; a.sc = c->sc.p; a.log_alpha = c->P.p + c->la_idx;
   a.gamma = (float)c->cfg.gamma; a.target_entropy = (float)(-c->A);
   a.auto_entropy = c->cfg.auto_entropy ? 1 : 0;
   a.ring = c->stats_ring.p; a.count = c->stats_cnt.p; a.ws = c->stats_ws.p; a.tl = c->tl_cur;
@@ -1234,6 +1253,9 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
   if (phase_mask & 1) {
     if (!have_batch)   // (have_batch: the previous update's rides / side stream produced them)
       enqueue_sample_gather(c, B, parity, dev_idx != 0, s);
+    // the reward of the set this update consumes, normalised once, with the factor current now
+    if (reward_norm_on(c) && mark(c, "reward_norm"))
+      launch_reward_norm(bb.r, bb.rn, B, c->rn_kc.p, c->tl_cur, s);
 
     // heads + sample for both stacks (networks_model1.py:78-99)
     HeadSampleArgs hs{};
@@ -1267,7 +1289,7 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
     {
       RowsFuse& rf = l5.b.rows;
       rf.kind = 1; rf.part = dotp(0); rf.nparts = c->nparts; rf.B = B;
-      rf.r = bb.r; rf.d = bb.d; rf.logp = c->logp.p; rf.logp_a = c->logp.p + B;
+      rf.r = batch_reward(c, bb); rf.d = bb.d; rf.logp = c->logp.p; rf.logp_a = c->logp.p + B;
       rf.gamma = (float)c->cfg.gamma;
       rf.sc = c->sc.p; rf.dq = c->dq.p; rf.dq4 = c->dq4.p; rf.loss_part = c->lpart_c.p;
       if (fb) {
@@ -1700,7 +1722,7 @@ static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_
                    (pr.parity ? 32 : 0) | (pr.have_batch ? 64 : 0) | (pr.ride_next ? 128 : 0) |
                    (c->mb_graph ? 256 : 0) | (c->per_feedback ? 512 : 0) |
                    (c->stats_on ? 1024 : 0) | (c->clip_on ? 2048 : 0) | (obs_norm_on(c) ? 4096 : 0) |
-                   (nstep_on(c) ? 8192 : 0),
+                   (nstep_on(c) ? 8192 : 0) | (reward_norm_on(c) ? 16384 : 0),
                use_ring ? c->ring_slots : 0,
                per_graph_len(c), reps};
   auto it = c->graphs.find(key);
@@ -2092,6 +2114,7 @@ int sacmi_device_count(int* n) {
 static void set_grad_clip(sacmi_ctx* c, double mc, double ma);
 static void set_obs_norm(sacmi_ctx* c, int32_t mode, double eps, double clip);
 static void set_nstep(sacmi_ctx* c, int32_t n);
+static void set_reward_norm(sacmi_ctx* c, int32_t mode, double scale, double eps, double clip);
 
 int sacmi_create(const sacmi_config* cfg, int device, sacmi_ctx** out) {
   return guard([&] {
@@ -2175,6 +2198,25 @@ int sacmi_create(const sacmi_config* cfg, int device, sacmi_ctx** out) {
       set_nstep(c.get(), (int32_t)n);
       CHECK_HIP(hipStreamSynchronize(c->stream));
     }
+    // SACMI_REWARD_NORM=1: running return normalisation from creation (sacmi_set_reward_norm mode
+    // 1, eps 1e-8, clip 10); SACMI_REWARD_SCALE=<x>: its scale, and on its own the constant-scale
+    // mode 3 without clipping
+    {
+      const char* rn = getenv("SACMI_REWARD_NORM");
+      const char* rs = getenv("SACMI_REWARD_SCALE");
+      const bool norm = rn && rn[0] == '1';
+      double scale = 1.0;
+      if (rs && rs[0]) {
+        char* end = nullptr;
+        scale = std::strtod(rs, &end);
+        REQUIRE(end != rs && *end == 0 && std::isfinite(scale) && scale > 0.0, SACMI_EVALUE,
+                "SACMI_REWARD_SCALE: expected a finite number > 0");
+      }
+      if (norm || (rs && rs[0])) {
+        set_reward_norm(c.get(), norm ? 1 : 3, scale, 1e-8, norm ? 10.0 : HUGE_VAL);
+        CHECK_HIP(hipStreamSynchronize(c->stream));
+      }
+    }
     *out = c.release();
   });
 }
@@ -2214,6 +2256,7 @@ int sacmi_destroy(sacmi_ctx* c) {
     c->clip_state.release(); c->clip_part.release(); c->gnorm_ring.release();
     c->on_mom.release(); c->on_vec.release(); c->on_actx.release();
     c->ns_tab.release(); c->ep_end.release(); c->ep_stage.release();
+    c->rn_state.release(); c->rn_kc.release(); c->rn.release(); c->rnb.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);
@@ -2448,6 +2491,19 @@ static void obs_stats_chunk(sacmi_ctx* c, const float* rows, int m) {
   sacmi::launch_obs_stats(oa, c->stream);
 }
 
+// One chunk through k_ret_stats (m == 0: the factor refreshed from the state and the settings as
+// they stand; reset: ret = 0 first)
+static void ret_stats_chunk(sacmi_ctx* c, const float* r, const float* d, const uint8_t* end, int m,
+                            bool reset) {
+  sacmi::RetStatsArgs ra{};
+  ra.r = r; ra.d = d; ra.end = end; ra.m = m; ra.reset = reset ? 1 : 0;
+  ra.use_state = c->rn_mode == 3 ? 0 : 1;
+  ra.gamma = (double)c->cfg.gamma; ra.scale = c->rn_scale; ra.eps = c->rn_eps;
+  ra.clip = (float)c->rn_clip;
+  ra.st = c->rn_state.p; ra.kc = c->rn_kc.p;
+  sacmi::launch_ret_stats(ra, c->stream);
+}
+
 // Rows [n] of transitions into the ring (deque(maxlen) semantics), from either layout:
 // separate arrays (packed == nullptr) or packed rows [n][2S + A + 2] = s | a | r | s2 | d.
 // `end` (sacmi_push_ep): the rows' episode-end flags, or null (all 0); while n-step returns are
@@ -2466,7 +2522,10 @@ static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float*
     // k_obs_stats sees it; rows already pending are flushed first, uncounted: they were pushed
     // before the mode was set)
     // (n-step returns on: likewise — the mailbox scatter carries no flags)
-    if (c->mb_host && !c->inflight && c->on_mode != 1 && !nstep_on(c) && c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
+    // (return statistics running, reward normalisation mode 1: likewise — k_ret_stats sees every
+    // row in push order; the frozen and constant-scale modes keep the mailbox)
+    if (c->mb_host && !c->inflight && c->on_mode != 1 && !nstep_on(c) && c->rn_mode != 1 &&
+        c->cfg.replay_kind == SACMI_REPLAY_UNIFORM &&
         c->mb_pending + n <= sacmi_ctx::kMbRows && c->mb_pending + n <= c->capacity) {
       // (rows pending beyond the capacity would map two rows onto one ring slot in the
       // sampler's scatter, stored in no fixed order: the chunked path's `skip` handles that)
@@ -2549,7 +2608,7 @@ static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float*
     // the chunk's flags in staging of their own beside slot k: the slot's wait above covers
     // them (push_zc_epoch / push_ev, recorded behind both copies)
     uint8_t* he = nullptr;
-    if (nstep_on(c)) {
+    if (nstep_on(c) || c->rn_mode == 1) {
       he = zc ? c->ep_zc_host[k] : c->ep_host[k];
       for (int64_t j = 0; j < m; ++j) he[j] = end && end[i + j] ? 1 : 0;
     }
@@ -2575,7 +2634,13 @@ static void push_impl(sacmi_ctx* c, const float* s, const float* a, const float*
     // scatter: the slot's reuse waits for this stream (push_zc_epoch / the copy's event, and
     // the next copy into `stage` is stream-ordered behind this reader)
     if (c->on_mode == 1) obs_stats_chunk(c, pa.stage, (int)m);
-    if (he) launch_ep_scatter(zc ? c->ep_zc_dev[k] : c->ep_stage.p, c->ep_end.p, m, pa.pos0, cap, c->stream);
+    const uint8_t* de = he ? (zc ? c->ep_zc_dev[k] : c->ep_stage.p) : nullptr;
+    if (nstep_on(c)) launch_ep_scatter(de, c->ep_end.p, m, pa.pos0, cap, c->stream);
+    // ... and its rewards, terminals and flags through the return recurrence, likewise (the
+    // rows ahead of a push of more than `capacity` rows are not stored: ret restarts at 0)
+    if (c->rn_mode == 1)
+      ret_stats_chunk(c, pa.stage + m * (S + A), pa.stage + m * (2 * S + A + 1), de, (int)m,
+                      skip > 0 && i == skip);
   }
   const int64_t added = n - skip;
   if (c->cfg.replay_kind == SACMI_REPLAY_PER) {
@@ -2600,14 +2665,16 @@ int sacmi_push_ep(sacmi_ctx* c, const float* s, const float* a, const float* r, 
                   const uint8_t* d, const uint8_t* end, int64_t n) {
   return guard([&] {
     REQUIRE(c, SACMI_EVALUE, "null ctx");
-    REQUIRE(nstep_on(c), SACMI_ESTATE, "n-step returns are off: no episode-end flags are kept");
+    REQUIRE(ep_flags_on(c), SACMI_ESTATE,
+            "n-step returns and return statistics are off: no episode-end flags are kept");
     pf_touch(c); push_impl(c, s, a, r, s2, d, nullptr, n, end); });
 }
 
 int sacmi_push_packed_ep(sacmi_ctx* c, const float* rows, const uint8_t* end, int64_t n) {
   return guard([&] {
     REQUIRE(c, SACMI_EVALUE, "null ctx");
-    REQUIRE(nstep_on(c), SACMI_ESTATE, "n-step returns are off: no episode-end flags are kept");
+    REQUIRE(ep_flags_on(c), SACMI_ESTATE,
+            "n-step returns and return statistics are off: no episode-end flags are kept");
     pf_touch(c); push_impl(c, nullptr, nullptr, nullptr, nullptr, nullptr, rows, n, end); });
 }
 
@@ -3119,10 +3186,10 @@ int sacmi_obs_norm_get_vectors(sacmi_ctx* c, float* nmean, float* nrstd, int32_t
 
 // ---------------------------------------------------------------------------
 // n-step returns in the gather (nstep.hip)
-static void nstep_alloc(sacmi_ctx* c) {
-  if (c->ep_end.p) return;
-  c->ns_tab.alloc((size_t)kNStepMax + 4);
-  c->ep_end.alloc((size_t)c->capacity);
+// the flags' staging beside the push's: n-step returns, and the return statistics' resets
+static void ep_staging_alloc(sacmi_ctx* c) {
+  static_assert(sacmi_ctx::kPushSlots == 2, "ep_host / ep_zc_host hold one entry per push slot");
+  if (c->ep_stage.p) return;
   c->ep_stage.alloc((size_t)c->push_rows);
   for (int i = 0; i < sacmi_ctx::kPushSlots; ++i) {
     CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->ep_host[i]), (size_t)c->push_rows,
@@ -3136,13 +3203,16 @@ static void nstep_alloc(sacmi_ctx* c) {
 static void set_nstep(sacmi_ctx* c, int32_t n) {
   REQUIRE(c, SACMI_EVALUE, "null ctx");
   REQUIRE(n >= 1 && n <= kNStepMax, SACMI_EVALUE, "n must be in [1, 32] (1: off)");
-  static_assert(sacmi_ctx::kPushSlots == 2, "ep_host / ep_zc_host hold one entry per push slot");
   pf_touch(c);
   mb_flush(c);      // (rows pushed while off reach the ring through the mailbox's scatter)
   const bool was_on = nstep_on(c);
   c->nstep = n;     // (on / off is part of the graph key; the value is device state)
   if (n == 1) return;
-  nstep_alloc(c);
+  ep_staging_alloc(c);
+  if (!c->ep_end.p) {
+    c->ns_tab.alloc((size_t)kNStepMax + 4);
+    c->ep_end.alloc((size_t)c->capacity);
+  }
   // off -> on: no row stored so far carries a flag
   if (!was_on) CHECK_HIP(hipMemsetAsync(c->ep_end.p, 0, (size_t)c->capacity, c->stream));
   // stream-ordered, the table by value: updates already enqueued keep the n they were enqueued under
@@ -3166,12 +3236,113 @@ int sacmi_nstep(sacmi_ctx* c, int32_t* n) {
 int sacmi_mark_episode_end(sacmi_ctx* c) {
   return guard([&] {
     REQUIRE(c, SACMI_EVALUE, "null ctx");
-    REQUIRE(nstep_on(c), SACMI_ESTATE, "n-step returns are off: no episode-end flags are kept");
+    REQUIRE(ep_flags_on(c), SACMI_ESTATE,
+            "n-step returns and return statistics are off: no episode-end flags are kept");
     REQUIRE(c->len > 0, SACMI_ESTATE, "the replay is empty");
     pf_touch(c);
     mb_flush(c);
-    const int64_t newest = (c->wpos - 1 + c->capacity) % c->capacity;
-    CHECK_HIP(hipMemsetAsync(c->ep_end.p + newest, 1, 1, c->stream));
+    if (nstep_on(c)) {
+      const int64_t newest = (c->wpos - 1 + c->capacity) % c->capacity;
+      CHECK_HIP(hipMemsetAsync(c->ep_end.p + newest, 1, 1, c->stream));
+    }
+    // the running return restarts with the next pushed row (stream-ordered; the moments stay)
+    if (c->rn_mode == 1 || c->rn_mode == 2) ret_stats_chunk(c, nullptr, nullptr, nullptr, 0, true);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// reward scaling and running return normalisation (retnorm.hip)
+static void refuse_reward_norm(const sacmi_ctx* c) {
+  REQUIRE(!(c && reward_norm_on(c)), SACMI_ESTATE,
+          "reward normalisation is on: no phase-split or data-parallel update (each rank's shard "
+          "would grow return statistics of its own; a collective over them is not built)");
+}
+
+static void reward_norm_alloc(sacmi_ctx* c) {
+  if (c->rn_state.p) return;
+  c->rn_state.alloc(4);
+  c->rn_kc.alloc(4);
+  c->rn.alloc((size_t)c->Bm);
+  c->rnb.alloc((size_t)c->Bm);
+  CHECK_HIP(hipMemsetAsync(c->rn_state.p, 0, 4 * sizeof(double), c->stream));
+}
+
+static void set_reward_norm(sacmi_ctx* c, int32_t mode, double scale, double eps, double clip) {
+  REQUIRE(c, SACMI_EVALUE, "null ctx");
+  REQUIRE(mode >= 0 && mode <= 3, SACMI_EVALUE,
+          "mode must be 0 (off), 1 (running), 2 (frozen) or 3 (constant scale)");
+  REQUIRE(std::isfinite(scale) && scale > 0.0, SACMI_EVALUE, "scale must be finite and > 0");
+  REQUIRE(std::isfinite(eps) && eps >= 0.0, SACMI_EVALUE, "eps must be finite and >= 0");
+  REQUIRE(clip > 0.0, SACMI_EVALUE, "clip must be > 0 or +inf");   // (false for a NaN)
+  pf_touch(c);
+  mb_flush(c);      // (rows pushed under the old mode reach the ring under it, uncounted)
+  c->rn_scale = scale;
+  c->rn_eps = eps;
+  c->rn_clip = clip;
+  c->rn_mode = mode;   // (on / off is part of the graph key; 1 / 2 / 3 is host state only)
+  if (mode == 0 && !c->rn_state.p) return;
+  reward_norm_alloc(c);
+  if (mode == 1 || mode == 2) ep_staging_alloc(c);
+  // stream-ordered: updates already enqueued keep the factor they were enqueued under
+  ret_stats_chunk(c, nullptr, nullptr, nullptr, 0, false);
+}
+
+int sacmi_set_reward_norm(sacmi_ctx* c, int32_t mode, double scale, double eps, double clip) {
+  return guard([&] { set_reward_norm(c, mode, scale, eps, clip); });
+}
+
+int sacmi_reward_norm(sacmi_ctx* c, int32_t* mode, double* scale, double* eps, double* clip) {
+  return guard([&] {
+    REQUIRE(c && mode && scale && eps && clip, SACMI_EVALUE, "null argument");
+    *mode = c->rn_mode;
+    *scale = c->rn_scale;
+    *eps = c->rn_eps;
+    *clip = c->rn_clip;
+  });
+}
+
+int sacmi_reward_norm_get_state(sacmi_ctx* c, double* count, double* mean, double* m2, double* ret) {
+  return guard([&] {
+    REQUIRE(c && count && mean && m2 && ret, SACMI_EVALUE, "null argument");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    double h[4] = {0.0, 0.0, 0.0, 0.0};     // (never switched on: nothing counted)
+    if (c->rn_state.p) CHECK_HIP(hipMemcpy(h, c->rn_state.p, sizeof(h), hipMemcpyDeviceToHost));
+    *count = h[0]; *mean = h[1]; *m2 = h[2]; *ret = h[3];
+  });
+}
+
+int sacmi_reward_norm_set_state(sacmi_ctx* c, double count, double mean, double m2, double ret) {
+  return guard([&] {
+    REQUIRE(c, SACMI_EVALUE, "null ctx");
+    REQUIRE(std::isfinite(count) && count >= 0.0, SACMI_EVALUE, "count must be finite and >= 0");
+    REQUIRE(std::isfinite(mean) && std::isfinite(ret) && std::isfinite(m2) && m2 >= 0.0, SACMI_EVALUE,
+            "mean and ret must be finite, m2 finite and >= 0");
+    pf_touch(c);
+    mb_flush(c);
+    reward_norm_alloc(c);
+    const double h[4] = {count, mean, m2, ret};
+    CHECK_HIP(hipMemcpyAsync(c->rn_state.p, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    ret_stats_chunk(c, nullptr, nullptr, nullptr, 0, false);
+    CHECK_HIP(hipStreamSynchronize(c->stream));   // (h leaves scope)
+  });
+}
+
+int sacmi_reward_norm_get_factor(sacmi_ctx* c, float* k) {
+  return guard([&] {
+    REQUIRE(c && k, SACMI_EVALUE, "null argument");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    *k = (float)c->rn_scale;             // (never switched on: the scale alone)
+    if (c->rn_kc.p) CHECK_HIP(hipMemcpy(k, c->rn_kc.p, 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int sacmi_read_batch_rn(sacmi_ctx* c, int32_t batch, float* rn) {
+  return guard([&] {
+    REQUIRE(c && rn, SACMI_EVALUE, "null argument");
+    REQUIRE(batch >= 1 && batch <= c->Bm, SACMI_EVALUE, "bad batch");
+    REQUIRE(c->rn.p, SACMI_ESTATE, "reward normalisation was never switched on");
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    CHECK_HIP(hipMemcpy(rn, c->rn.p, (size_t)batch * 4, hipMemcpyDeviceToHost));
   });
 }
 
@@ -3221,6 +3392,7 @@ int sacmi_debug_set_done(sacmi_ctx* c, const int64_t* slots, const float* values
 int sacmi_step_phase(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_scale) {
   return guard([&] {
     refuse_obs_norm(c);
+    refuse_reward_norm(c);
     pf_touch(c);
     refuse_feedback(c);
     REQUIRE(phase >= 0 && phase <= 3, SACMI_EVALUE, "phase must be 0, 1, 2 or 3");
@@ -3233,6 +3405,7 @@ int sacmi_step_phase_ex(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_s
                         int32_t parity, int32_t have_batch, int32_t ride_next) {
   return guard([&] {
     refuse_obs_norm(c);
+    refuse_reward_norm(c);
     pf_touch(c);
     refuse_feedback(c);
     REQUIRE(phase >= 0 && phase <= 3, SACMI_EVALUE, "phase must be 0, 1, 2 or 3");
@@ -3297,6 +3470,7 @@ int sacmi_dp_loopback_init(sacmi_ctx* c, int32_t world) {
 int sacmi_step_dp(sacmi_ctx* c, int32_t batch, int32_t n_updates) {
   return guard([&] {
     refuse_obs_norm(c);
+    refuse_reward_norm(c);
     refuse_clip_sharded(c, c->dp_shard && (c->dp_world > 1 || c->dp_loopback || dp_phases_at_world1()));
     pf_touch(c);
     refuse_feedback(c);

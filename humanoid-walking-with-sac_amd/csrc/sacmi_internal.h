@@ -694,6 +694,36 @@ void launch_gather_nstep(const GatherArgs& a, const NStepArgs& ns, const ObsNorm
 void launch_ep_scatter(const uint8_t* stage, uint8_t* ep_end, int64_t n, int64_t pos0, int64_t cap,
                        hipStream_t s);
 
+// Reward scaling and running return normalisation (retnorm.hip; sacmi_set_reward_norm).  Device
+// state, one per context, allocated when first switched on:
+//   st [4] fp64: count | mean | M2 of the discounted returns seen | ret, the running return
+//   kc [2] fp32: the factor k | clip — what the per-update k_reward_norm reads through pointers
+// y = clamp(r * k, -clip, clip) in fp32: one rounding; compares, not fminf / fmaxf: a NaN stays
+// a NaN
+__device__ __forceinline__ float reward_normalize(float r, float k, float c) {
+  const float t = r * k;
+  return t < -c ? -c : (t > c ? c : t);
+}
+constexpr int kRetRowLanes = 16;    // Welford lanes of k_ret_stats: lane l takes rows l, l + 16, ...
+constexpr int kRetMaxRows = 1024;   // rows per chunk (the push chunk)
+// One pushed chunk r[m], d[m], end[m] (device or host-mapped memory; end: null = all 0) through
+// the return recurrence into the running moments, and the factor refreshed.  m == 0: the factor
+// alone (new state, scale or eps).  reset: ret = 0 before the first row (the rows ahead of it
+// were not stored, or an episode end was marked).  use_state 0: k = (float)scale (mode 3)
+struct RetStatsArgs {
+  const float* r;
+  const float* d;
+  const uint8_t* end;
+  int m, reset, use_state;
+  double gamma, scale, eps;
+  float clip;
+  double* st;
+  float* kc;
+};
+void launch_ret_stats(const RetStatsArgs& a, hipStream_t s);
+// rn[b] = reward_normalize(r[b], kc[0], kc[1]) for b < B, out of place
+void launch_reward_norm(const float* r, float* rn, int B, const float* kc, tl_word* tl, hipStream_t s);
+
 // Rows sacmi_push left in host-mapped staging for the next synchronous update (the
 // trainer's row per env step): that update's sampler kernel scatters them into the ring
 // before it draws, instead of a scatter launch of their own ahead of the update

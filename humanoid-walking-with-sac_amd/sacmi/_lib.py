@@ -112,6 +112,13 @@ _PROTOS = {
     "sacmi_get_episode_ends": [c_vp, c_i64p, ctypes.c_int64, ctypes.c_int32, c_u8p],
     "sacmi_read_batch_rd": [c_vp, ctypes.c_int32, c_f32p, c_f32p],
     "sacmi_debug_set_done": [c_vp, c_i64p, c_f32p, ctypes.c_int64],
+    "sacmi_set_reward_norm": [c_vp, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double],
+    "sacmi_reward_norm": [c_vp, c_i32p, c_f64p, c_f64p, c_f64p],
+    "sacmi_reward_norm_get_state": [c_vp, c_f64p, c_f64p, c_f64p, c_f64p],
+    "sacmi_reward_norm_set_state": [c_vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double],
+    "sacmi_reward_norm_get_factor": [c_vp, c_f32p],
+    "sacmi_read_batch_rn": [c_vp, ctypes.c_int32, c_f32p],
     "sacmi_step_phase": [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_float],
     "sacmi_grad_buffer": [c_vp, ctypes.c_int, ctypes.POINTER(c_vp), c_i64p],
     "sacmi_grad_arena_numel": [c_vp, c_i64p],

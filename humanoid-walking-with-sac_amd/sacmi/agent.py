@@ -13,6 +13,7 @@ without a HIP device raises.
 """
 from __future__ import annotations
 
+import math
 import random
 
 import numpy as np
@@ -133,8 +134,20 @@ class SAC:
                  per_beta_start: float = 0.4, per_beta_frames: int = 100000,
                  diagnostics: bool = False, max_grad_norm=None,
                  normalize_obs: bool = False, obs_clip: float = 10.0, obs_norm_eps: float = 1e-8,
-                 n_step: int = 1):
-        """``n_step``: multi-step returns, 1..32 (1: the reference's one-step target).  Every
+                 n_step: int = 1, reward_scale: float = 1.0, normalize_reward: bool = False,
+                 reward_clip=None, reward_norm_eps: float = 1e-8):
+        """``reward_scale`` / ``normalize_reward``: the reward as the update sees it.  The replay
+        keeps raw rewards; every update's minibatch reward becomes ``clamp(r * k, -reward_clip,
+        reward_clip)``.  ``normalize_reward=True``: ``k = reward_scale / sqrt(var + reward_norm_eps)``
+        with the running population variance of the discounted return of the rows pushed so far
+        (one environment stream; the return restarts behind a terminal row, an
+        ``episode_end=True`` row or ``replay_buffer.mark_episode_end()``), ``reward_clip`` 10 unless
+        given.  ``reward_scale != 1`` alone: ``k = reward_scale``, no clipping unless
+        ``reward_clip`` is given.  With ``n_step > 1`` the n-step return is what is scaled and
+        clipped.  ``reward_norm_state()`` / ``set_reward_norm_state()`` read and set the
+        statistics, ``freeze_reward_norm()`` stops pushes from updating them; checkpoints carry
+        them.
+        ``n_step``: multi-step returns, 1..32 (1: the reference's one-step target).  Every
         sampled row's target becomes r_0 + gamma r_1 + ... + gamma^m r_m + gamma^(m+1) (min Q -
         alpha log pi)(s'_m), the chain of stored rows cut at a terminal, at an episode end
         (``replay_buffer.push(..., episode_end=True)`` or ``replay_buffer.mark_episode_end()``
@@ -232,6 +245,12 @@ class SAC:
             self._ctx.set_obs_norm(1, float(obs_norm_eps), float(obs_clip))
         if int(n_step) > 1:
             self._ctx.set_nstep(int(n_step))
+        if normalize_reward:
+            self._ctx.set_reward_norm(1, float(reward_scale), float(reward_norm_eps),
+                                      10.0 if reward_clip is None else float(reward_clip))
+        elif float(reward_scale) != 1.0 or reward_clip is not None:
+            self._ctx.set_reward_norm(3, float(reward_scale), float(reward_norm_eps),
+                                      math.inf if reward_clip is None else float(reward_clip))
         st = random.getstate()             # device sampling stream starts at `random`'s
         self._ctx.set_mt(0, np.array(st[1][:624], np.uint32), st[1][624])
         self._mt_adopted = st[1]           # (the Python stream state the device holds)
@@ -418,6 +437,49 @@ class SAC:
         self._ctx.set_obs_norm_moments(float(e["count"]), np.asarray(e["mean"], np.float64),
                                        np.asarray(e["m2"], np.float64))
 
+    # -- reward scaling / return normalisation (SAC(normalize_reward=True)) -------------------
+    def reward_norm_state(self):
+        """``{"count", "mean", "var", "ret"}``: the returns counted, their running mean and
+        population variance, and the running discounted return of the episode being pushed."""
+        self._flush_device()
+        count, mean, m2, ret = self._ctx.reward_norm_state()
+        return {"count": count, "mean": mean, "var": m2 / count if count > 0 else 0.0, "ret": ret}
+
+    def set_reward_norm_state(self, count, mean, var, ret=0.0):
+        """Replace the running statistics (e.g. with those of another run)."""
+        self._flush_device()
+        self._ctx.set_reward_norm_state(float(count), float(mean), float(var) * float(count), float(ret))
+
+    def freeze_reward_norm(self, flag=True):
+        """``True``: pushes stop updating the statistics (they keep normalising); ``False``:
+        they resume.  Needs ``normalize_reward=True``."""
+        mode, scale, eps, clip = self._ctx.reward_norm()
+        if mode not in (1, 2):
+            raise RuntimeError("return normalisation is off (SAC(normalize_reward=True))")
+        self._flush_device()       # (rows staged so far are counted under the mode they met)
+        self._ctx.set_reward_norm(2 if flag else 1, scale, eps, clip)
+
+    def _reward_norm_entry(self):
+        """The checkpoint entry (None while the feature is off)."""
+        mode, scale, eps, clip = self._ctx.reward_norm()
+        if mode == 0:
+            return None
+        self._flush_device()
+        count, mean, m2, ret = self._ctx.reward_norm_state()
+        return {"mode": int(mode), "scale": float(scale), "eps": float(eps), "clip": float(clip),
+                "state": torch.tensor([count, mean, m2, ret], dtype=torch.float64)}
+
+    def _load_reward_norm(self, ck):
+        """Restore a checkpoint's settings and statistics; a checkpoint without the entry leaves
+        everything as it is."""
+        e = ck.get("reward_norm")
+        if e is None:
+            return
+        self._flush_device()
+        self._ctx.set_reward_norm(int(e["mode"]), float(e["scale"]), float(e["eps"]), float(e["clip"]))
+        st = np.asarray(e["state"], np.float64).reshape(4)
+        self._ctx.set_reward_norm_state(*[float(x) for x in st])
+
     def fetch_diagnostics(self, max_rows=4096):
         """The most recent updates' diagnostics rows, oldest first, as dicts keyed by
         ``sacmi.STAT_NAMES`` ([] unless the agent was built with ``diagnostics=True``)."""
@@ -442,6 +504,9 @@ class SAC:
         on = self._obs_norm_entry()
         if on is not None:
             ck["obs_norm"] = on
+        rn = self._reward_norm_entry()
+        if rn is not None:
+            ck["reward_norm"] = rn
         torch.save(ck, path)
 
     def load(self, path):
@@ -449,6 +514,7 @@ class SAC:
         self._load_nets(ck)
         self.alpha = ck["alpha"]
         self._load_obs_norm(ck)
+        self._load_reward_norm(ck)
 
     def _load_nets(self, ck):
         for name in ("policy", "q1", "q2", "q1_target", "q2_target"):
@@ -489,6 +555,9 @@ class SAC:
         on = self._obs_norm_entry()
         if on is not None:
             ck["obs_norm"] = on
+        rn = self._reward_norm_entry()
+        if rn is not None:
+            ck["reward_norm"] = rn
         # NB: the reference only calls torch.save when replay_buffer=True (an
         # indentation slip at sac_imp.py:198-201); the drop-in always saves.
         torch.save(ck, path)
@@ -521,18 +590,24 @@ class SAC:
         if "alpha_optimizer_state_dict" in ck and self.automatic_entropy_tuning:
             self.alpha_optimizer.load_state_dict(ck["alpha_optimizer_state_dict"])
         self._load_obs_norm(ck)
+        self._load_reward_norm(ck)
         if n_step != self.n_step:
             self._ctx.set_nstep(n_step)
         if rows is not None:
             # the checkpoint's statistics already count these rows: frozen around the reload
             mode, eps, clip = self._ctx.obs_norm()
+            rmode, rscale, reps, rclip = self._ctx.reward_norm()
             if mode == 1:
                 self._ctx.set_obs_norm(2, eps, clip)
+            if rmode == 1:
+                self._ctx.set_reward_norm(2, rscale, reps, rclip)
             try:
                 self.replay_buffer._replace_arrays(*rows, episode_end=ends)
             finally:
                 if mode == 1:
                     self._ctx.set_obs_norm(1, eps, clip)
+                if rmode == 1:
+                    self._ctx.set_reward_norm(1, rscale, reps, rclip)
         return ck.get("episode", 0), ck.get("total_steps", 0)
 
     def _checkpoint_rows(self, rb):

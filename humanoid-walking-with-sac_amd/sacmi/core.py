@@ -154,8 +154,8 @@ class Context:
 
     # -- replay --------------------------------------------------------------------
     def push(self, s, a, r, s2, d, episode_end=None) -> None:
-        """``episode_end`` (bool per row, n-step returns on only): the rows' episode-end flags
-        (sacmi.h sacmi_push_ep)."""
+        """``episode_end`` (bool per row; n-step returns or return statistics on only): the rows'
+        episode-end flags (sacmi.h sacmi_push_ep)."""
         S, A = self.cfg.state_dim, self.cfg.action_dim
         s = np.ascontiguousarray(s, np.float32).reshape(-1, S)
         n = s.shape[0]
@@ -402,6 +402,55 @@ class Context:
         nmean, nrstd = np.zeros(S, np.float32), np.zeros(S, np.float32)
         L.call("sacmi_obs_norm_get_vectors", self._h, L.fptr(nmean), L.fptr(nrstd), S)
         return nmean, nrstd
+
+    # -- reward scaling / return normalisation (sacmi.h sacmi_set_reward_norm) ----------
+    def set_reward_norm(self, mode: int = 1, scale: float = 1.0, eps: float = 1e-8,
+                        clip: float = 10.0) -> None:
+        """The ring keeps raw rewards; every update normalises its minibatch's,
+        ``clamp(r * k, -clip, clip)`` with ``k = scale / sqrt(var(discounted return) + eps)``.
+        ``mode`` 0: off, 1: running (pushes update the statistics), 2: frozen, 3: constant
+        scale only (``k = scale``).  ``clip = math.inf``: none."""
+        L.call("sacmi_set_reward_norm", self._h, int(mode), float(scale), float(eps), float(clip))
+        self._rn_mode = int(mode)
+
+    def reward_norm(self):
+        """(mode, scale, eps, clip) in effect."""
+        mode = ctypes.c_int32()
+        scale, eps, clip = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        L.call("sacmi_reward_norm", self._h, ctypes.byref(mode), ctypes.byref(scale), ctypes.byref(eps),
+               ctypes.byref(clip))
+        self._rn_mode = int(mode.value)
+        return int(mode.value), float(scale.value), float(eps.value), float(clip.value)
+
+    def reward_norm_mode(self) -> int:
+        """The mode in effect, mirrored on the host (the drop-in buffers ask at every flush)."""
+        m = getattr(self, "_rn_mode", None)
+        if m is None:                       # (SACMI_REWARD_NORM may have set it at creation)
+            m = self.reward_norm()[0]
+        return m
+
+    def reward_norm_state(self):
+        """(count, mean, m2, ret) float64: the moments of the discounted returns seen (m2: the
+        sum of squared deviations from the mean) and the running return.  Synchronises."""
+        v = [ctypes.c_double() for _ in range(4)]
+        L.call("sacmi_reward_norm_get_state", self._h, *[ctypes.byref(x) for x in v])
+        return tuple(float(x.value) for x in v)
+
+    def set_reward_norm_state(self, count: float, mean: float, m2: float, ret: float = 0.0) -> None:
+        L.call("sacmi_reward_norm_set_state", self._h, float(count), float(mean), float(m2), float(ret))
+
+    def reward_norm_factor(self) -> float:
+        """The fp32 factor k the update's normalising launch reads.  Synchronises."""
+        k = ctypes.c_float()
+        L.call("sacmi_reward_norm_get_factor", self._h, ctypes.byref(k))
+        return float(k.value)
+
+    def read_batch_rn(self, batch: int) -> np.ndarray:
+        """Test hook: the normalised r[batch] of batch set 0 as the last update left it
+        (``read_batch_rd`` keeps returning the raw gathered one)."""
+        rn = np.zeros(batch, np.float32)
+        L.call("sacmi_read_batch_rn", self._h, int(batch), L.fptr(rn))
+        return rn
 
     def step_phase(self, batch: int, phase: int, grad_scale: float = 1.0, parity: int = 0,
                    have_batch: bool = False, ride_next: bool = False) -> None:

@@ -52,9 +52,12 @@ class _Staged:
         if not self._rows:
             return
         ctx = self._ctx
-        nstep = ctx.nstep() >= 2
+        # the flags cut the n-step chains and reset the running return of the return statistics
+        nstep = ctx.nstep() >= 2 or ctx.reward_norm_mode() in (1, 2)
         if not nstep and any(self._ends):
-            raise ValueError("episode_end needs n-step returns on (Context.set_nstep / SAC(n_step=))")
+            raise ValueError("episode_end needs n-step returns or return statistics on "
+                             "(Context.set_nstep / SAC(n_step=), Context.set_reward_norm / "
+                             "SAC(normalize_reward=True))")
         S, A = ctx.cfg.state_dim, ctx.cfg.action_dim
         n = len(self._rows)
         # packed rows s | a | r | s2 | d in a reused buffer (sacmi_push_packed)
@@ -77,7 +80,8 @@ class _Staged:
 
     def push(self, state, action, reward, next_state, done, episode_end=False):
         """``episode_end``: this row is its episode's last although ``done`` is False (a
-        step-limit cut); kept with the row, used by the n-step gather (Context.set_nstep)."""
+        step-limit cut); kept with the row, used by the n-step gather (Context.set_nstep), and
+        where the running return of the return statistics restarts (Context.set_reward_norm)."""
         self._ensure_ctx(state, action)
         self._rows.append((state, action, reward, next_state, done))
         self._ends.append(bool(episode_end))
@@ -142,7 +146,7 @@ class _Staged:
             return
         self._ensure_ctx(s[0], a[0])
         self._ctx.replay_clear()
-        if episode_end is not None and self._ctx.nstep() >= 2:
+        if episode_end is not None and (self._ctx.nstep() >= 2 or self._ctx.reward_norm_mode() in (1, 2)):
             self._ctx.push(s, a, r, s2, d, episode_end=episode_end)
         else:
             self._ctx.push(s, a, r, s2, d)

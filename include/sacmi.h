@@ -386,7 +386,8 @@ int sacmi_obs_norm_get_vectors(sacmi_ctx* ctx, float* nmean, float* nrstd, int32
  * overwritten with its slot; switching on from off clears all flags (stream-ordered).
  * sacmi_push_ep / sacmi_push_packed_ep are sacmi_push / sacmi_push_packed with end: [n] u8 or
  * NULL (all 0); sacmi_mark_episode_end sets the flag of the newest stored row (a trainer that
- * learns of a time-limit cut only after the push).  All three return SACMI_ESTATE while off;
+ * learns of a time-limit cut only after the push).  All three return SACMI_ESTATE while off
+ * (unless the return statistics of sacmi_set_reward_norm take the flags, modes 1 and 2);
  * sacmi_mark_episode_end also with an empty replay.  A terminal row needs no flag.
  *
  * On / off selects another captured graph; the value of n and the table are stream-ordered
@@ -413,6 +414,83 @@ int sacmi_get_episode_ends(sacmi_ctx* ctx, const int64_t* idx, int64_t n, int32_
  * sacmi_read_batch); raw fp32 values into the ring's done array at ring slots. */
 int sacmi_read_batch_rd(sacmi_ctx* ctx, int32_t batch, float* r, float* d);
 int sacmi_debug_set_done(sacmi_ctx* ctx, const int64_t* slots, const float* values, int64_t n);
+
+/* ---- reward scaling and running return normalisation ---------------------------------- */
+/* A constant reward scale (the SAC paper's one sensitive hyperparameter) and the running return
+ * normaliser of the mainstream stacks (the norm_reward of a VecNormalize wrapper): the reward is
+ * divided by the running standard deviation of the discounted return, then clipped.  As with
+ * the observations, the ring stores RAW rewards; they are normalised where they are consumed,
+ * at sample time, with the statistics current then.  The reference has neither.
+ *
+ * State, per context, on the device, all fp64: ret, the running discounted return of the
+ * episode being pushed, and count, mean, M2 (the sum of squared deviations from the mean) of
+ * the ret values seen.  With g64 = (double)cfg.gamma, for every transition a push actually
+ * stores, in push order (ONE environment stream: consecutive rows are consecutive steps),
+ *     ret = fl64(fl64(ret * g64) + (double)r_i)         two roundings, never contracted
+ *     (count, mean, M2) take ret                         Welford steps, Chan's merge
+ *     if d_i != 0 or end_i: ret = 0
+ * end_i is the row's episode-end flag (below).  A push of more than `capacity` rows counts only
+ * the rows it stores, and ret is reset to 0 before the first of them.  sacmi_replay_clear
+ * leaves the state alone.  Each chunk of at most 1024 rows that reaches the device is merged in
+ * a fixed order without atomics, every word with one writer (never E[x^2] - mean^2): the same
+ * pushes from the same state give the same bits.
+ *
+ * Factor, one fp32 value, recomputed on the device whenever the state, scale or eps changes:
+ *     k = (float)(scale / sqrt(M2 / count + eps))       fp64, rounded once; modes 1 and 2, count > 0
+ *     k = (float)scale                                  mode 3, or count == 0
+ * (eps = 0 with all returns equal gives an infinite k: keep eps > 0.)
+ *
+ * Normalisation, one device function, in fp32:
+ *     t = r * k                                         one rounding
+ *     y = t < -clip ? -clip : (t > clip ? clip : t)     compares: a NaN stays a NaN
+ * applied to the gathered reward of every minibatch row, by one small launch of its own in every
+ * update behind whatever produced the minibatch (k_reward_norm, out of place).  With n-step
+ * returns on it is applied to the collapsed return R: the clip then bounds R * k, not each
+ * step's reward.  States, actions and d are untouched.  Everything downstream is then in
+ * normalised units, exactly as if the user had pushed such rewards: the Q values, the
+ * diagnostics' REWARD_MEAN, Q_* and TD_*, the prioritized feedback's priorities and the gradient
+ * norms.  A NaN reward stays a NaN in the row; in mode 1 it also enters ret and the moments,
+ * after which k is NaN until sacmi_reward_norm_set_state replaces them.
+ *
+ * mode 0: off (default; the update's launches are exactly those of a context that never called
+ * this).  1: running: pushes update the state.  2: frozen: pushes leave the whole state alone,
+ * ret included.  3: constant scale only: no state is kept, k = (float)scale.  scale > 0 and
+ * finite, eps >= 0 and finite, clip > 0 or +inf (no clipping), else SACMI_EVALUE.  On / off
+ * selects another captured graph; the mode among 1 / 2 / 3, the state, scale, eps and clip are
+ * stream-ordered device or host state: changing them re-captures nothing.  Switching modes
+ * leaves the state alone.  Every call here that changes what the normalisation would read gives
+ * up a batch drawn ahead.
+ *
+ * The gathers are unchanged: they ride along and are drawn ahead as without the feature
+ * (sacmi_step_ride_possible reports what it reports for a context that never enabled it).
+ * While the mode is 1 every pushed row takes the chunked device path (the push mailbox is
+ * bypassed; rows already pending are flushed first, uncounted); modes 2 and 3 keep the mailbox.
+ *
+ * Episode ends: in modes 1 and 2 sacmi_push_ep, sacmi_push_packed_ep and sacmi_mark_episode_end
+ * are accepted even while n-step returns are off.  The flags then feed only the return reset:
+ * the ring's flag bytes are still not kept and sacmi_get_episode_ends still reports zeros.
+ * sacmi_mark_episode_end also sets ret = 0, stream-ordered (modes 1 and 2).  With n-step off
+ * and this mode 0 or 3 the three calls return SACMI_ESTATE as before.
+ *
+ * In any mode but 0, sacmi_step_phase, sacmi_step_phase_ex and sacmi_step_dp (loopback
+ * included) return SACMI_ESTATE before touching state: rank-local statistics would need a
+ * collective that is not built.  (The constant-scale data-parallel case needs none; it is the
+ * follow-up.)
+ *
+ * SACMI_REWARD_NORM=1 in the environment at sacmi_create selects mode 1 with scale 1, eps 1e-8
+ * and clip 10; SACMI_REWARD_SCALE=<x> sets the scale, and on its own selects mode 3 with clip
+ * +inf.  Additive: the ABI version is unchanged. */
+int sacmi_set_reward_norm(sacmi_ctx* ctx, int32_t mode, double scale, double eps, double clip);
+int sacmi_reward_norm(sacmi_ctx* ctx, int32_t* mode, double* scale, double* eps, double* clip);
+/* Synchronises the stream.  All zero on a context that never switched the feature on. */
+int sacmi_reward_norm_get_state(sacmi_ctx* ctx, double* count, double* mean, double* m2, double* ret);
+/* count < 0, m2 < 0 or a non-finite value: SACMI_EVALUE.  Works in every mode. */
+int sacmi_reward_norm_set_state(sacmi_ctx* ctx, double count, double mean, double m2, double ret);
+/* the factor k as k_reward_norm reads it (synchronises) */
+int sacmi_reward_norm_get_factor(sacmi_ctx* ctx, float* k);
+/* Test hook: the normalised r[batch] of minibatch set 0 as the last update left it;
+ * sacmi_read_batch_rd keeps returning the raw gathered r. */
+int sacmi_read_batch_rn(sacmi_ctx* ctx, int32_t batch, float* rn);
 
 /* Data-parallel split of the step (one process per GPU).  phase 0: sample, gather,
  * forward, critic backward -> critic gradient buffer; phase 1: critic Adam + Polyak,

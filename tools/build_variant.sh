@@ -8,7 +8,7 @@ PKG=$(cd "$(dirname "$0")/../humanoid-walking-with-sac_amd" && pwd)
 name=$1; shift
 mkdir -p "$PKG/build"
 objs=""
-for src in sacmi kernels replay per stats clip obsnorm nstep; do
+for src in sacmi kernels replay per stats clip obsnorm nstep retnorm; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result \
     -fno-gpu-rdc $1 -c "$PKG/csrc/$src.hip" -o "$PKG/build/${src}_$name.o" &
   objs="$objs $PKG/build/${src}_$name.o"
