@@ -130,6 +130,17 @@ struct DevBuf {
   }
 };
 
+// The phases a launch enqueues (phase_mask; UpdatePlan's three functions); fused: all of them,
+// Adam in the weight-gradient levels.  StepThenCritic: the previous update's actor step, then
+// the next update's critic phase
+enum : int { kPhaseCritic = 1, kPhaseActor = 2, kPhaseActorStep = 4, kPhaseFused = 7, kPhaseStepThenCritic = 5 };
+// GraphKey::phase_mask carries, above the phases, everything else a captured update depends on
+enum : int {
+  kKeyGradScale = 8, kKeyKeepGrads = 16, kKeyParity = 32, kKeyHaveBatch = 64, kKeyRideNext = 128,
+  kKeyMailbox = 256, kKeyFeedback = 512, kKeyStats = 1024, kKeyClip = 2048, kKeyObsNorm = 4096,
+  kKeyNStep = 8192, kKeyRewardNorm = 16384,
+};
+
 struct GraphKey {
   int batch, dev_idx, dev_eps, phase_mask, ring;
   int64_t per_len;   // PER launch geometry depends on the fill
@@ -209,7 +220,6 @@ struct sacmi_ctx {
   sacmi::DevBuf<uint32_t> mt_pf;    // [625]: the random stream before the draw ahead
   bool pf_on = true;                // SACMI_NO_PREFETCH at creation: off
   bool pf_valid = false;            // a drawn-ahead batch waits in set pf_parity
-  bool pf_save = false;             // (enqueue_update: the draw ahead saves mt_pf)
   bool pf_touched = false;          // another call since the last single update: draw
                                     //   nothing ahead (a push per update would drop it)
   int pf_parity = 0, pf_B = 0;
@@ -325,7 +335,6 @@ struct sacmi_ctx {
   // sharded optimizer step (ZeRO-1): reduce-scatter the gradients, Adam on this rank's
   // 1/world of the parameters, all-gather the parameters (enqueue_dp)
   bool dp_shard = false;
-  bool dp_sharding_now = false;   // enqueue_dp is enqueueing a sharded sequence
   // a sharded step ran at world >= 2: each rank's Adam moments are current on its own chunks
   // only — reading them (tensors, checkpoints) or stepping them (any non-sharded update)
   // raises until sacmi_dp_sync_state gathers them
@@ -982,47 +991,91 @@ static void enqueue_sample_gather(sacmi_ctx* c, int B, int parity, bool dev_idx,
   }
 }
 
-// The data-parallel Adam step of one range over the whole range: critic (+ Polyak, + the q
-// losses) or actor (+ the alpha step, policy loss, loss ring), grad_scale = 1/world
-static AdamArgs dp_adam_args(sacmi_ctx* c, bool critic, int B, float grad_scale, bool use_ring) {
-  AdamArgs ad{};
+// The two parameter ranges an optimizer step covers: the twin critics, or the policy with
+// log_alpha behind it
+struct ParamRange { int64_t begin, end; };
+static ParamRange param_range(const sacmi_ctx* c, bool critic) {
+  return critic ? ParamRange{c->q_begin, c->q_end} : ParamRange{c->pi_begin, c->total};
+}
+
+// The weight tensors of a range in the order every consumer walks them (q1 / q2 layer by
+// layer, or the policy's layers then its head), each with the Adam step counter that drives
+// its bias corrections and its gradient-clipping group within the range
+struct RangeSeg { Linear lin; int step_idx, group; };
+static std::vector<RangeSeg> range_segments(const sacmi_ctx* c, bool critic) {
+  std::vector<RangeSeg> segs;
+  for (int l = 0; l <= c->nh; ++l) {
+    for (int i = 0; critic && i < 2; ++i) segs.push_back(RangeSeg{c->q_fc[i][l], 1 + i, i});
+    if (!critic) segs.push_back(RangeSeg{l < c->nh ? c->p_fc[l] : c->p_head, 0, 0});
+  }
+  return segs;
+}
+
+// One optimizer step, whichever launch takes it: the critics' (+ Polyak, + the q losses) or the
+// actor's (+ the alpha step, the policy loss, the loss ring).  Host-only: kept as the k_adam
+// arguments it determines (the segments, grad_scale and the collective's flags are the launch's
+// own: dp_adam_args) and where the fused levels also store the gradients (keep_grads, else null);
+// fill() gives it to a fused weight-gradient level (L6, L13) or to a k_adam launch.
+struct OptStep { AdamArgs ad; float* G_export; };
+// host_words: the graph belongs to a synchronous step (sacmi_step, _launch / _wait), whose
+// step_finish reads the host-mapped loss / error words of both steps and the done word behind
+// the actor's.  Every other graph (losses through the ring, phase-split, data-parallel) stores
+// none of them: no store over the host link, no system-scope fence in the scalar chains.
+static OptStep opt_step(const sacmi_ctx* c, bool critic, int B, bool use_ring, bool host_words) {
+  OptStep o{};
+  o.G_export = c->keep_grads ? c->G.p : nullptr;
+  AdamArgs& ad = o.ad;
   ad.p = c->P.p; ad.g = c->G.p; ad.m = c->M.p; ad.v = c->V.p;
-  ad.nseg = 0;
-  const int nh = c->nh, nb = (B + 31) / 32;
-  auto seg = [&](const Linear& l, int idx) {
-    REQUIRE(ad.nseg < kMaxAdamSegs, SACMI_ESTATE, "too many Adam segments");
-    ad.seg[ad.nseg++] = AdamSeg{l.off, l.numel_padded(), idx};
-  };
-  if (critic) {
-    for (int layer = 0; layer <= nh; ++layer)
-      for (int i = 0; i < 2; ++i) seg(c->q_fc[i][layer], i == 0 ? 1 : 2);
-  } else {
-    for (int l = 0; l <= nh; ++l) seg(l < nh ? c->p_fc[l] : c->p_head, 0);
-  }
-  ad.total = 0;
-  for (int i = 0; i < ad.nseg; ++i) {
-    REQUIRE(ad.seg[i].n % 4 == 0 && ad.seg[i].off % 4 == 0, SACMI_ESTATE, "Adam segment not float4-aligned");
-    ad.total += ad.seg[i].n;
-  }
-  ad.lr = (float)c->cfg.lr; ad.beta1 = 0.9f; ad.beta2 = 0.999f; ad.eps = 1e-8f; ad.grad_scale = grad_scale;
-  ad.sc = c->sc.p; ad.n_part = nb; ad.loss_div = (float)B;
+  ad.lr = (float)c->cfg.lr; ad.beta1 = 0.9f; ad.beta2 = 0.999f; ad.eps = 1e-8f;
+  ad.sc = c->sc.p; ad.loss_div = (float)B;
+  ad.n_part = (B + 31) / 32;     // loss partials: one per 32-row block of L5 / L9
   // the bf16 shadows of the updated parameters / targets (read by the bf16 level kernels)
   ad.ph = c->Ph.p; ad.tgth = c->Th.p;
+  ad.loss_host = host_words ? c->loss_host_dev : nullptr;
   if (critic) {
     ad.tgt = c->T.p; ad.tgt_base = c->q_begin;
     ad.tau = (float)c->cfg.tau; ad.step_offset = 1;
     ad.loss_part = c->lpart_c.p; ad.loss_slot0 = 0; ad.n_losses = 2;
     ad.log_alpha_idx = -1; ad.auto_entropy = 0;
     ad.err_skip = kErrSkipAll; ad.err_nopolyak = kErrActLike;
-    // every rank's error flags, summed by the critic gradient collective (kDpFlagN): past the
-    // critic range (all-reduce form), or in their own buffer (sharded form)
-    ad.err_flags = c->dp_sharding_now ? c->dp_flags.p : c->G.p + c->q_end;
   } else {
     ad.tgt = nullptr; ad.tau = 0.f; ad.step_offset = 0;
     ad.loss_part = c->lpart_a.p; ad.loss_slot0 = 2; ad.n_losses = 1;
     ad.log_alpha_idx = c->la_idx; ad.auto_entropy = c->cfg.auto_entropy;
     ad.loss_ring = use_ring ? c->ring.p : nullptr; ad.ring = c->ring_slots;
+    ad.done_word = host_words ? reinterpret_cast<int*>(c->loss_host_dev + 4) : nullptr;
     ad.err_skip = ~0; ad.err_nopolyak = 0;
+  }
+  return o;
+}
+static void fill(AdamArgs& ad, const OptStep& o) { ad = o.ad; }
+static void fill(AdamFuse& f, const OptStep& o) {
+  const AdamArgs& a = o.ad;
+  f.P = a.p; f.M = a.m; f.V = a.v; f.T = a.tgt; f.G = o.G_export;
+  f.t_base = a.tgt_base; f.Ph = a.ph; f.Th = a.tgth;
+  f.lr = a.lr; f.beta1 = a.beta1; f.beta2 = a.beta2; f.eps = a.eps; f.tau = a.tau;
+  f.step_offset = a.step_offset; f.sc = a.sc;
+  f.loss_part = a.loss_part; f.n_part = a.n_part; f.loss_slot0 = a.loss_slot0; f.n_losses = a.n_losses;
+  f.loss_div = a.loss_div; f.log_alpha_idx = a.log_alpha_idx; f.auto_entropy = a.auto_entropy;
+  f.log_alpha_grad = a.log_alpha_idx >= 0 ? a.g + a.log_alpha_idx : nullptr;
+  f.loss_ring = a.loss_ring; f.ring = a.ring; f.loss_host = a.loss_host; f.done_word = a.done_word;
+  f.err_skip = a.err_skip; f.err_nopolyak = a.err_nopolyak;
+}
+
+// The Adam launch (k_adam) of one step over its whole range, grad_scale = 1/world.  err_flags:
+// every rank's error flags, summed by the critic gradient collective (kDpFlagN), or null
+static AdamArgs dp_adam_args(const sacmi_ctx* c, bool critic, const OptStep& o, float grad_scale,
+                             const float* err_flags) {
+  AdamArgs ad{};
+  fill(ad, o);
+  ad.grad_scale = grad_scale;
+  ad.err_flags = err_flags;
+  for (const RangeSeg& sg : range_segments(c, critic)) {
+    REQUIRE(ad.nseg < kMaxAdamSegs, SACMI_ESTATE, "too many Adam segments");
+    const AdamSeg a{sg.lin.off, sg.lin.numel_padded(), sg.step_idx};
+    REQUIRE(a.n % 4 == 0 && a.off % 4 == 0, SACMI_ESTATE, "Adam segment not float4-aligned");
+    ad.seg[ad.nseg++] = a;
+    ad.total += a.n;
   }
   return ad;
 }
@@ -1102,11 +1155,8 @@ static void enqueue_stats(sacmi_ctx* c, int B, const BatchBufs& bb, hipStream_t 
 static void clip_alloc(sacmi_ctx* c) {
   if (c->clip_state.p) return;
   int64_t n[3] = {0, 0, 0};
-  for (int l = 0; l <= c->nh; ++l) {
-    n[0] += c->q_fc[0][l].numel_padded();
-    n[1] += c->q_fc[1][l].numel_padded();
-    n[2] += (l < c->nh ? c->p_fc[l] : c->p_head).numel_padded();
-  }
+  for (bool critic : {true, false})   // groups: q1, q2, then the policy
+    for (const RangeSeg& sg : range_segments(c, critic)) n[(critic ? 0 : 2) + sg.group] += sg.lin.numel_padded();
   for (int k = 0; k < 3; ++k) c->clip_wgs[k] = clip_workgroups(n[k]);
   c->clip_state.alloc(1);
   c->clip_part.alloc((size_t)c->clip_wgs[0] + c->clip_wgs[1] + c->clip_wgs[2]);
@@ -1126,24 +1176,14 @@ static void enqueue_clip_adam(sacmi_ctx* c, AdamArgs ad, bool critic, const char
   gs.part = c->clip_part.p + part0;
   gs.wg_begin[0] = 0;
   for (int k = 0; k < gs.ngroups; ++k) gs.wg_begin[k + 1] = gs.wg_begin[k] + c->clip_wgs[(critic ? 0 : 2) + k];
-  auto seg = [&](const Linear& l, int group) {
+  // (range_segments: the list dp_adam_args cut ad.seg from, so seg_group[i] is ad.seg[i]'s group)
+  for (const RangeSeg& sg : range_segments(c, critic)) {
+    const Linear& l = sg.lin;
     REQUIRE(gs.nseg < kMaxAdamSegs, SACMI_ESTATE, "too many clip segments");
     REQUIRE(l.off % 4 == 0 && l.ld % 4 == 0 && l.kdim() <= l.ld, SACMI_ESTATE, "clip segment not float4-aligned");
     check_span(gs.g + l.off, l.numel_padded() - 1, "clip gradient segment");
-    gs.seg[gs.nseg++] = ClipSeg{l.off, l.n_out, l.ld, l.kdim(), group};
-  };
-  // (the segments in dp_adam_args' order: the Adam launch's seg_group is the same list)
-  if (critic) {
-    for (int layer = 0; layer <= c->nh; ++layer)
-      for (int i = 0; i < 2; ++i) seg(c->q_fc[i][layer], i);
-  } else {
-    for (int l = 0; l <= c->nh; ++l) seg(l < c->nh ? c->p_fc[l] : c->p_head, 0);
-  }
-  REQUIRE(gs.nseg == ad.nseg, SACMI_ESTATE, "clip segments do not match the Adam step's");
-  for (int i = 0; i < gs.nseg; ++i) {
-    REQUIRE(gs.seg[i].off == ad.seg[i].off && (int64_t)gs.seg[i].rows * gs.seg[i].ld == ad.seg[i].n,
-            SACMI_ESTATE, "clip segments do not match the Adam step's");
-    ad.seg_group[i] = gs.seg[i].group;
+    ad.seg_group[gs.nseg] = sg.group;
+    gs.seg[gs.nseg++] = ClipSeg{l.off, l.n_out, l.ld, l.kdim(), sg.group};
   }
   check_span(gs.part, gs.wg_begin[gs.ngroups] - 1, "clip partials", 8);
   check_span(c->clip_state.p, 0, "clip state", (int)sizeof(ClipState));
@@ -1162,294 +1202,312 @@ static void enqueue_clip_adam(sacmi_ctx* c, AdamArgs ad, bool critic, const char
   }
 }
 
-// Feedback mode, update r of a multi-update graph that has a successor, called once r's L5 is
-// enqueued: the side stream forks here, writes update r's priorities back, then draws and
-// gathers update r + 1's batch (into the other set); update r + 1 joins on side_ev[2r + 3].
-static void fork_feedback(sacmi_ctx* c, int B, int r) {
+// Update r of a multi-update graph that has a successor: the side stream forks here, then draws
+// and gathers update r + 1's batch (into the other set); update r + 1 joins on side_ev[2r + 3].
+// Feedback mode (write_back), called once r's L5 is enqueued: it first writes update r's
+// priorities back.
+static void fork_next_draw(sacmi_ctx* c, int B, int r, bool write_back) {
   CHECK_HIP(hipEventRecord(c->side_ev[2 * r], c->stream));
   CHECK_HIP(hipStreamWaitEvent(c->side_stream, c->side_ev[2 * r], 0));
-  enqueue_feedback(c, B, batch_bufs(c, r & 1), c->side_stream);
+  if (write_back) enqueue_feedback(c, B, batch_bufs(c, r & 1), c->side_stream);
   enqueue_sample_gather(c, B, (r + 1) & 1, true, c->side_stream, "_next");
   CHECK_HIP(hipEventRecord(c->side_ev[2 * r + 3], c->side_stream));
 }
 
-// parity: which batch buffer set this update uses; have_batch: its indices and rows
-// were produced by the previous update's ride-along work; ride_next: produce the next
-// update's (into the other set) inside this update's L11 / L13 launches.
-// fork_r (feedback mode): >= 0 for update fork_r of a multi-update graph that has a successor —
-// fork_feedback runs behind its L5; -1: the write-back is this update's last launch.
-static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_mask,
-                           float grad_scale, bool use_ring, int parity = 0,
-                           bool have_batch = false, bool ride_next = false, int fork_r = -1) {
-  hipStream_t s = c->stream;
-  const bool fb = feedback_on(c, dev_idx);
-  REQUIRE(!fb || phase_mask == 7, SACMI_ESTATE, "prioritized feedback needs the fused update");
-  // every Adam step of this update but the sharded data-parallel form's own (enqueue_dp_sharded
-  // steps this rank's chunks) reads and writes the whole of M, V
-  if ((phase_mask & 6) && !c->dp_sharding_now) require_moments_whole(c);
-  REQUIRE(!(own_gather(c) && ride_next), SACMI_ESTATE,
-          "observation normalisation or n-step returns on: no gather rides along or is drawn ahead");
-  c->site_counter = 0;
-  const BatchBufs bb = batch_bufs(c, parity);
-  // where the next update's sampling + gather ride: L12 / L13 (placement A, batch <= ~2k,
-  // any phase split) or L6 / L10 (placement B, fused updates of the batch-4096 class)
-  const bool ride_b = ride_next && !ride_possible(c, B);
-  REQUIRE(!ride_b || (phase_mask == 7 && ride_b_possible(c, B)), SACMI_ESTATE,
-          "no ride-along placement for this batch");
-  const int S = c->S, A = c->A, H = c->H, Kx = c->Kx, Hd = c->Hd;
-  float* P = c->P.p;
-  float* G = c->G.p;
-  const float* T = c->T.p;
-  const int nb = (B + 31) / 32;     // loss partials: one per 32-row block of L5 / L9
-  // Fused updates whose losses leave through the ring (sacmi_step_async, _many_async, the
-  // one-rank sacmi_step_dp, the timeline's replicas; use_ring is part of the graph key): nobody
-  // reads the host-mapped loss / error / done words (step_finish alone does, and it follows
-  // the synchronous forms' graphs only), so these graphs store none of them: no store over
-  // the host link and no system-scope fence in the fused levels' scalar chains
-  const bool ring_only = use_ring && phase_mask == 7;
-  auto W = [&](const Linear& l) { return P + l.off; };
-  // fc3 dot partials: slot 0/1 q1/q2 (L2), 2/3 target q1/q2 (L4), 4/5 updated q1/q2 (L8)
-  auto dotp = [&](int slot) { return c->dotp.p + (size_t)slot * B * c->nparts; };
-  auto with_dot = [&](GemmDesc g, const float* w3, int slot) {
-    g.dotw = w3; g.dotp = dotp(slot); g.dotp_ld = c->nparts;
-    return g;
-  };
-  auto Wt = [&](const Linear& l) { return T + (l.off - c->q_begin); };
-  auto dW = [&](const Linear& l) { return G + l.off; };
-  const Linear(&q)[2][4] = c->q_fc;
+// Batch-set control of one update (the multi-update graphs, the draw-ahead, the data-parallel
+// driver's captured sequences): parity = this update's minibatch buffer set; have_batch = its
+// indices and rows were produced by the previous update's ride-along work or side stream;
+// ride_next = produce the next update's (into the other set) inside this update's launches.
+struct PhaseRide {
+  int parity = 0;
+  bool have_batch = false, ride_next = false;
+  // feedback mode: >= 0 for update fork_r of a multi-update graph that has a successor —
+  // fork_next_draw runs behind its L5; -1: the write-back is this update's last launch
+  int fork_r = -1;
+  bool save_mt = false;   // ride_next draws ahead for the next launch: its sampler saves mt_pf
+  // a phase of the sharded data-parallel sequence (enqueue_dp), which steps this rank's chunks
+  // of both ranges itself and keeps the error flags in a buffer of their own
+  bool sharded = false;
+};
+
+// One enqueue_update: which phases, on what, for whom
+struct UpdateOpts {
+  int B = 0, dev_idx = 1, dev_eps = 1;   // (dev_*: sampled / drawn on the device, 0: staged)
+  int phase_mask = kPhaseFused;
+  float grad_scale = 1.f;
+  bool use_ring = false;                 // the losses leave through the loss ring
+  PhaseRide ride;
+};
+
+// Can Polyak ride in the policy's dhp1 level (L12)?  Where that level leaves CUs idle on k_gemm
+// (batch <= ~1k): off the critic Adam level, the longest of the update; every critic step (L6,
+// k_adam, the sharded chunks) then leaves the targets alone.  Where it cannot, the critic's step
+// takes the targets with it, and the sharded sequence runs a pass of its own.
+static bool polyak_rides(const sacmi_ctx* c, int B, int phase_mask) {
+  return (phase_mask & kPhaseActor) && !act16_on(c, B) &&
+         (int64_t)((B + 31) / 32) * ((c->H + 31) / 32) <= 192;
+}
+static PolyakArgs polyak_args(const sacmi_ctx* c) {
+  return PolyakArgs{c->T.p, c->P.p + c->q_begin, c->Th.p, (c->q_end - c->q_begin) / 4, (float)c->cfg.tau, c->sc.p};
+}
+
+// One pass of the twin critics (q1 | q2 side by side): its input rows, whether it runs on the
+// target arena, its hidden activations per layer and the first of its two head dot-partial
+// slots: on (s, a) (slots 0 / 1), the targets on (s2, a') (2 / 3), the updated critics on (s, a~)
+struct CriticPass { const float* x; bool target; const sacmi::DevBuf<float>* h; int slot0; };
+
+// One update's plan: what its phases share (arenas, activation format, batch set) and the phases
+struct UpdatePlan {
+  sacmi_ctx* const c;
+  const UpdateOpts o;
+  const hipStream_t s = c->stream;
+  const BatchBufs bb = batch_bufs(c, o.ride.parity);
+  const int B = o.B, S = c->S, A = c->A, H = c->H, Kx = c->Kx, Hd = c->Hd;
   const int nh = c->nh, L = nh - 1;   // L: the last hidden layer (its head is layer nh)
-  auto shadow = [&](const float* b) -> const unsigned short* {
+  float* const P = c->P.p; float* const G = c->G.p;
+  // bf16 activations (act16_on): element offsets are in the update's activation format
+  const bool act16 = act16_on(c, B); const int a16 = act16 ? 1 : 0;
+  const bool fb = feedback_on(c, o.dev_idx);
+  // single-GPU update: Adam in the dW epilogues — unless the gradients are clipped: the norm
+  // needs the whole gradient before any of it is consumed, so the dW levels store to the arena
+  // (same reduction order, same bits) and the Adam steps follow in launches of their own
+  const bool fuse = o.phase_mask == kPhaseFused && !c->clip_on;
+  const bool host_words = o.phase_mask == kPhaseFused && !o.use_ring;   // (opt_step)
+  // where the next update's sampling + gather ride: L12 / L13 (placement A, batch <= ~2k,
+  // any phase split) or L6 / L12 (placement B, fused updates of the batch-4096 class)
+  const bool ride_b = o.ride.ride_next && !ride_possible(c, B);
+  const bool polyak_ride = polyak_rides(c, B, o.phase_mask);
+
+  bool fused() const { return o.phase_mask == kPhaseFused; }
+  float* W(const Linear& l) const { return P + l.off; }
+  float* dW(const Linear& l) const { return G + l.off; }
+  const float* Wq(const CriticPass& cp, const Linear& l) const {   // in the arena the pass runs on
+    return cp.target ? c->T.p + (l.off - c->q_begin) : W(l);
+  }
+  // where a dW level stores: the parameters (fused Adam) or the gradient arena
+  float* dst(const Linear& l) const { return fuse ? W(l) : dW(l); }
+  // fc3 dot partials: slot 0/1 q1/q2 (L2), 2/3 target q1/q2 (L4), 4/5 updated q1/q2 (L8)
+  float* dotp(int slot) const { return c->dotp.p + (size_t)slot * B * c->nparts; }
+  float* E(float* base, size_t off) const {
+    return act16 ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(base) + off) : base + off;
+  }
+  float* hpa(int l) const { return E(c->hp[l].p, (size_t)B * Hd); }   // the policy's actor rows
+  GemmDesc fw(GemmDesc g) const { g.a16 = a16; g.c16 = a16; return g; }        // forward level
+  GemmDesc dh(GemmDesc g) const { g.x16 = a16; g.a16 = g.axk == 1 ? a16 : 0; return g; }   // dh level
+  GemmDesc dwx(GemmDesc g) const { g.b16 = a16; return g; }                     // dW level (X)
+  // this update's error flags for the critic gradient collective (kDpFlagN): past the critic
+  // range (all-reduce form), or in their own buffer (sharded form)
+  float* err_flags() const { return o.ride.sharded ? c->dp_flags.p : G + c->q_end; }
+  const unsigned short* shadow(const float* b) const {
     if (!c->Ph.p || !b) return nullptr;
     if (b >= c->P.p && b < c->P.p + c->P.n) return c->Ph.p + (b - c->P.p);
     if (b >= c->T.p && b < c->T.p + c->T.n) return c->Th.p + (b - c->T.p);
     return nullptr;
-  };
-  // activation buffers: element offsets in the update's activation format
-  const bool act16 = act16_on(c, B);
-  const int a16 = act16 ? 1 : 0;
-  auto E = [&](float* base, size_t off) -> float* {
-    return act16 ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(base) + off) : base + off;
-  };
-  auto fw = [&](GemmDesc g) { g.a16 = a16; g.c16 = a16; return g; };        // forward level
-  auto dh = [&](GemmDesc g) { g.x16 = a16; g.a16 = g.axk == 1 ? a16 : 0; return g; };   // dh level
-  auto dwx = [&](GemmDesc g) { g.b16 = a16; return g; };                     // dW level (X)
-  auto run = [&](Level& lv, const std::string& name) {
+  }
+  void run(Level& lv, const char* name) const {
     lv.b.bf16 = c->bf16 ? 1 : 0;
     for (int i = 0; i < lv.b.count; ++i) lv.b.d[i].Bh = shadow(lv.b.d[i].B);
     lv.b.ws = c->dw_ws.p;
     lv.b.ws_floats = (int64_t)c->dw_ws.n;
     validate_batch(lv.b);
-    if (mark(c, name.c_str(), level_flops(lv.b), level_bytes(lv.b))) {
+    if (mark(c, name, level_flops(lv.b), level_bytes(lv.b))) {
       lv.b.tl = c->tl_cur;
       launch_gemm(lv.b, s);
     }
-  };
+  }
+  // k_adam in a fused level's place or as a data-parallel step (clipped: behind k_grad_sumsq)
+  void run_adam(AdamArgs ad, bool critic, const char* name) const {
+    if (c->clip_on) {
+      enqueue_clip_adam(c, ad, critic, name, s);
+    } else if (mark(c, name)) {
+      ad.tl = c->tl_cur;
+      launch_adam(ad, s);
+    }
+  }
 
-  // fused updates whose policy dhp1 level (L12) leaves CUs idle on k_gemm: Polyak rides there
-  // (data-parallel phase 1, both optimizer forms: the critic Adam before L7 leaves the
-  // targets alone — sharded: enqueue_dp's chunk Adam, all-reduce: the one below)
-  const bool polyak_ride = (phase_mask == 7 || (phase_mask & 2)) &&
-                           !act16 && (int64_t)((B + 31) / 32) * ((H + 31) / 32) <= 192;
-  if (phase_mask & 1) {
-    if (!have_batch)   // (have_batch: the previous update's rides / side stream produced them)
-      enqueue_sample_gather(c, B, parity, dev_idx != 0, s);
+  // ---- the twin critics' levels: each appends q1's then q2's GEMM to lv.  fc1 on [x|1|a]:
+  void add_critic_fc1(Level& lv, const CriticPass& cp) const {
+    const Linear(&q)[2][4] = c->q_fc;
+    for (int i = 0; i < 2; ++i)
+      lv.add(fw(gd(cp.x, Kx, 1, Wq(cp, q[i][0]), Kx, 1, E(cp.h[0].p, (size_t)i * Hd), 2 * Hd, B, H, S + A + 1, EPI_RELU)));
+  }
+  // hidden layer l >= 1 (K = H, bias in the epilogue); the last one also accumulates the critic
+  // head (fc3 / fc4) dot partials into the pass's slots
+  void add_critic_hidden(Level& lv, const CriticPass& cp, int l) const {
+    const Linear(&q)[2][4] = c->q_fc;
+    for (int i = 0; i < 2; ++i) {
+      GemmDesc g = fw(gd_fwd_h(E(cp.h[l - 1].p, (size_t)i * Hd), 2 * Hd, Wq(cp, q[i][l]), Hd,
+                               E(cp.h[l].p, (size_t)i * Hd), 2 * Hd, B, H, H));
+      if (l == L) { g.dotw = Wq(cp, q[i][nh]); g.dotp = dotp(cp.slot0 + i); g.dotp_ld = c->nparts; }
+      lv.add(g);
+    }
+  }
+  // the row-prologue dh level: d[L-1] = (d[L] W[L]) * relu'(h[L-1]), the A operand d[L] =
+  // coef * w_head * [h[L] > 0] formed from h[L] on the fly once the row prologue (RowsFuse
+  // `kind`, returned: the caller sets its pass-specific fields) has finished the heads from the dot
+  // partials; store_u: the coefficient-free rows u are stored once into d[L] by the
+  // column-tile-0 workgroups, for the weight gradient of layer L
+  RowsFuse& add_critic_dh_rows(Level& lv, const CriticPass& cp, const sacmi::DevBuf<float>* d, int kind,
+                               bool store_u) const {
+    const Linear(&q)[2][4] = c->q_fc;
+    for (int i = 0; i < 2; ++i) {
+      GemmDesc g = gd(E(cp.h[L].p, (size_t)i * Hd), 2 * Hd, 1, W(q[i][L]), Hd, 0, d[L - 1].p + i * H, 2 * H,
+                      B, H, H, EPI_MASK, E(cp.h[L - 1].p, (size_t)i * Hd), 2 * Hd);
+      g.axk = 1; g.ax_slot = i; g.ax_w = W(q[i][nh]);
+      if (store_u) { g.ax_ld = 2 * H; g.ax_out = d[L].p + i * H; }
+      lv.add(dh(g));
+    }
+    RowsFuse& rf = lv.b.rows;
+    rf.kind = kind; rf.part = dotp(cp.slot0); rf.nparts = c->nparts; rf.B = B; rf.sc = c->sc.p;
+    return rf;
+  }
+  // the dh levels below it (3 hidden layers): d[l-1] = (d[l] W[l]) * relu'(h[l-1]) down to d[0]
+  void add_critic_dh(Level& lv, const CriticPass& cp, const sacmi::DevBuf<float>* d, int l) const {
+    const Linear(&q)[2][4] = c->q_fc;
+    for (int i = 0; i < 2; ++i)
+      lv.add(dh(gd(d[l].p + i * H, 2 * H, 1, W(q[i][l]), Hd, 0, d[l - 1].p + i * H, 2 * H,
+                   B, H, H, EPI_MASK, E(cp.h[l - 1].p, (size_t)i * Hd), 2 * Hd)));
+  }
+
+  // Phase 0: the minibatch, the policy and critic forward passes, the target, the critic backward
+  // and every critic weight gradient (L1 - L6)
+  void enqueue_critic_phase() const {
+    const Linear(&q)[2][4] = c->q_fc;
+    if (!o.ride.have_batch)   // (have_batch: the previous update's rides / side stream produced them)
+      enqueue_sample_gather(c, B, o.ride.parity, o.dev_idx != 0, s);
     // the reward of the set this update consumes, normalised once, with the factor current now
     if (reward_norm_on(c) && mark(c, "reward_norm"))
       launch_reward_norm(bb.r, bb.rn, B, c->rn_kc.p, c->tl_cur, s);
-
     // heads + sample for both stacks (networks_model1.py:78-99)
     HeadSampleArgs hs{};
     hs.h = c->hp[L].p; hs.Wh = W(c->p_head); hs.rows = 2 * B; hs.A = A; hs.K = H;
-    hs.ldh = Hd; hs.ldw = Hd; hs.eps = c->eps.p; hs.gen_eps = dev_eps; hs.seed = c->cfg.seed;
+    hs.ldh = Hd; hs.ldw = Hd; hs.eps = c->eps.p; hs.gen_eps = o.dev_eps; hs.seed = c->cfg.seed;
     hs.sc = c->sc.p; hs.act = E(bb.x2, (size_t)S + 1); hs.ldact = Kx; hs.logp = c->logp.p;
-    hs.h16 = a16;
-    hs.cache = c->cache.p;
+    hs.h16 = a16; hs.cache = c->cache.p;
     hs.scale = (float)((c->cfg.action_high - c->cfg.action_low) / 2);
     hs.bias = (float)((c->cfg.action_high + c->cfg.action_low) / 2);
     hs.logp_part = c->lp_part.p; hs.split_row = B;    // sums of log pi(a~|s) for dL/dlog_alpha
     // Normal validation of policy.sample(next_state) / policy.sample(state) (sac_imp.py:89,116)
     hs.nan_flag = &c->sc.p->err; hs.nan_bit_lo = ERR_NAN_TGT; hs.nan_bit_hi = ERR_NAN_ACT;
-    // single-GPU update: Adam in the dW epilogues — unless the gradients are clipped: the norm
-    // needs the whole gradient before any of it is consumed, so the dW levels store to the arena
-    // (same reduction order, same bits) and the Adam steps follow in launches of their own
-    const bool fuse = phase_mask == 7 && !c->clip_on;
-    // L5: dh[L-1] = (dh[L] W[L]) * relu'(h[L-1]), with the target / critic-loss rows folded
-    // in: the row prologue finishes q1, q2, qt1, qt2 from the dot partials and gives
-    // dq_i = 2 (q_i - q^) / B; the A operand dh[L] = dq * w_head * [h[L] > 0] is formed
-    // from h[L] on the fly (its coefficient-free rows u stored once by the column-tile-0
-    // workgroups, for the weight gradient of layer L)
+    const CriticPass own{bb.xq, false, c->hq, 0}, tgt{bb.x2, true, c->hqt, 2};
+    // L5: dh[L-1] with the target / critic-loss rows folded in: the row prologue finishes q1, q2,
+    // qt1, qt2 from the dot partials and gives dq_i = 2 (q_i - q^) / B
     Level l5;
-    for (int i = 0; i < 2; ++i) {
-      GemmDesc g = gd(E(c->hq[L].p, (size_t)i * Hd), 2 * Hd, 1, W(q[i][L]), Hd, 0, c->dhc[L - 1].p + i * H, 2 * H,
-                      B, H, H, EPI_MASK, E(c->hq[L - 1].p, (size_t)i * Hd), 2 * Hd);
-      g.axk = 1; g.ax_slot = i; g.ax_w = W(q[i][nh]); g.ax_ld = 2 * H;
-      g.ax_out = c->dhc[L].p + i * H;   // the coefficient-free rows u (layer L's weight gradient)
-      l5.add(dh(g));
-    }
-    {
-      RowsFuse& rf = l5.b.rows;
-      rf.kind = 1; rf.part = dotp(0); rf.nparts = c->nparts; rf.B = B;
-      rf.r = batch_reward(c, bb); rf.d = bb.d; rf.logp = c->logp.p; rf.logp_a = c->logp.p + B;
-      rf.gamma = (float)c->cfg.gamma;
-      rf.sc = c->sc.p; rf.dq = c->dq.p; rf.dq4 = c->dq4.p; rf.loss_part = c->lpart_c.p;
-      if (fb) {
-        rf.w = bb.w; rf.td = bb.td;
-        check_span(rf.w, B - 1, "rows w");
-        check_span(rf.td, B - 1, "rows td");
-      }
+    RowsFuse& rf = add_critic_dh_rows(l5, own, c->dhc, 1, true);
+    rf.r = batch_reward(c, bb); rf.d = bb.d; rf.logp = c->logp.p; rf.logp_a = c->logp.p + B;
+    rf.gamma = (float)c->cfg.gamma;
+    rf.dq = c->dq.p; rf.dq4 = c->dq4.p; rf.loss_part = c->lpart_c.p;
+    if (fb) {
+      rf.w = bb.w; rf.td = bb.td;
+      check_span(rf.w, B - 1, "rows w");
+      check_span(rf.td, B - 1, "rows td");
     }
     // L1: policy fc1 on [s2 ; s] (2B rows), critic fc1 (twin) on [s|1|a]
     Level l1;
     l1.add(fw(gd(bb.x2, Kx, 1, W(c->p_fc[0]), c->p_fc[0].ld, 1, c->hp[0].p, Hd, 2 * B, H, S + 1, EPI_RELU)));
-    for (int i = 0; i < 2; ++i)
-      l1.add(fw(gd(bb.xq, Kx, 1, W(q[i][0]), Kx, 1, E(c->hq[0].p, (size_t)i * Hd), 2 * Hd, B, H, S + A + 1, EPI_RELU)));
+    add_critic_fc1(l1, own);
     run(l1, "gemm_L1_fc1");
-    // L2 (.. L2b): the remaining hidden layers (K = H, bias in the epilogue); the last one
-    // also accumulates the critic head (fc3 / fc4) dot partials of q1 / q2 (slots 0 / 1)
+    // L2 (.. L2b): the remaining hidden layers; the last one: the dot partials of q1 / q2
     for (int l = 1; l < nh; ++l) {
       Level lv;
       lv.add(fw(gd_fwd_h(c->hp[l - 1].p, Hd, W(c->p_fc[l]), Hd, c->hp[l].p, Hd, 2 * B, H, H)));
-      for (int i = 0; i < 2; ++i) {
-        GemmDesc g = fw(gd_fwd_h(E(c->hq[l - 1].p, (size_t)i * Hd), 2 * Hd, W(q[i][l]), Hd,
-                                 E(c->hq[l].p, (size_t)i * Hd), 2 * Hd, B, H, H));
-        if (l == L) g = with_dot(g, W(q[i][nh]), i);
-        lv.add(g);
-      }
+      add_critic_hidden(lv, own, l);
       run(lv, l == 1 ? "gemm_L2_fc2" : "gemm_L2b_fc3");
     }
     if (mark(c, "heads_sample", 2.0 * 2 * B * (2.0 * A) * H)) {
       hs.tl = c->tl_cur;
       launch_heads_sample(hs, s);
     }
-    // L3/L4 (.. L4b): target critics on [s2|1|a'] (head dot partials: slots 2 / 3)
+    // L3/L4 (.. L4b): target critics on [s2|1|a']
     {
       Level l3;
-      for (int i = 0; i < 2; ++i)
-        l3.add(fw(gd(bb.x2, Kx, 1, Wt(q[i][0]), Kx, 1, E(c->hqt[0].p, (size_t)i * Hd), 2 * Hd, B, H, S + A + 1, EPI_RELU)));
+      add_critic_fc1(l3, tgt);
       run(l3, "gemm_L3_tgt_fc1");
     }
     for (int l = 1; l < nh; ++l) {
       Level lv;
-      for (int i = 0; i < 2; ++i) {
-        GemmDesc g = fw(gd_fwd_h(E(c->hqt[l - 1].p, (size_t)i * Hd), 2 * Hd, Wt(q[i][l]), Hd,
-                                 E(c->hqt[l].p, (size_t)i * Hd), 2 * Hd, B, H, H));
-        lv.add(l == L ? with_dot(g, Wt(q[i][nh]), 2 + i) : g);
-      }
+      add_critic_hidden(lv, tgt, l);
       run(lv, l == 1 ? "gemm_L4_tgt_fc2" : "gemm_L4b_tgt_fc3");
     }
     run(l5, "gemm_L5_critic_dh1");
-    if (fb && fork_r >= 0) fork_feedback(c, B, fork_r);
-    // L5b (3 hidden layers): dh[l-1] = (dh[l] W[l]) * relu'(h[l-1]) down to dh[0]
+    if (fb && o.ride.fork_r >= 0) fork_next_draw(c, B, o.ride.fork_r, true);
+    // L5b (3 hidden layers)
     for (int l = L - 1; l >= 1; --l) {
       Level lv;
-      for (int i = 0; i < 2; ++i)
-        lv.add(dh(gd(c->dhc[l].p + i * H, 2 * H, 1, W(q[i][l]), Hd, 0, c->dhc[l - 1].p + i * H, 2 * H,
-                     B, H, H, EPI_MASK, E(c->hq[l - 1].p, (size_t)i * Hd), 2 * Hd)));
+      add_critic_dh(lv, own, c->dhc, l);
       run(lv, "gemm_L5b_critic_dh");
     }
     // L6: every critic weight gradient: into the gradient arena, or (fused) straight into
     // Adam + Polyak on the parameters.  The hidden weights are read by the dh levels
     // above, so every critic dW runs here — in both modes, so the reduction order (and
-    // the bits) are the same.  Where the policy's dhp1 level (L12) leaves CUs idle and runs
-    // on k_gemm (batch <= ~1k), the Polyak step rides there instead (polyak_ride): off the
-    // critic Adam level, the longest of the update
-    auto dst = [&](const Linear& l) { return fuse ? P + l.off : dW(l); };
+    // the bits) are the same.  (polyak_ride: the Polyak step rides in L12 instead)
     const int wepi = fuse ? (polyak_ride ? EPI_ADAM : EPI_ADAM_POLYAK) : EPI_STORE;
     Level l6;
     for (int i = 0; i < 2; ++i)
       l6.add(dwx(gd(c->dhc[0].p + i * H, 2 * H, 0, bb.xq, Kx, 0, dst(q[i][0]), Kx, H, S + A + 1, B,
-                    wepi, nullptr, 0, 1 + i)));
+                      wepi, nullptr, 0, 1 + i)));
     for (int i = 0; i < 2; ++i) {
       for (int l = 1; l < L; ++l)
         l6.add(dwx(gd_dw_h(c->dhc[l].p + i * H, 2 * H, E(c->hq[l - 1].p, (size_t)i * Hd), 2 * Hd,
-                           dst(q[i][l]), Hd, H, H, B, wepi, 1 + i)));
+                             dst(q[i][l]), Hd, H, H, B, wepi, 1 + i)));
       // L5 stored u = dh[L] / coef (the coefficient factored out of its rows): the layer-L
       // weight gradient applies coef = dL/dq_i (dq) as a per-batch-row K-scale
       GemmDesc wl = dwx(gd_dw_h(c->dhc[L].p + i * H, 2 * H, E(c->hq[L - 1].p, (size_t)i * Hd), 2 * Hd,
-                                dst(q[i][L]), Hd, H, H, B, wepi, 1 + i));
+                                  dst(q[i][L]), Hd, H, H, B, wepi, 1 + i));
       wl.a_ksc = c->dq.p + i * B;
       l6.add(wl);
       l6.add(dwx(gd_dw_h(c->dq4.p + (size_t)i * B * 4, 4, E(c->hq[L].p, (size_t)i * Hd), 2 * Hd, dst(q[i][nh]), Hd, 1, H, B,
-                         wepi, 1 + i)));
+                           wepi, 1 + i)));
     }
     if (fuse) {
-      AdamFuse& f = l6.b.adam;
       l6.b.has_adam = 1;
-      f.P = P; f.M = c->M.p; f.V = c->V.p; f.T = c->T.p; f.G = c->keep_grads ? G : nullptr;
-      f.t_base = c->q_begin;
-      f.lr = (float)c->cfg.lr; f.beta1 = 0.9f; f.beta2 = 0.999f; f.eps = 1e-8f;
-      f.tau = (float)c->cfg.tau; f.step_offset = 1; f.sc = c->sc.p;
-      f.loss_part = c->lpart_c.p; f.n_part = nb; f.loss_slot0 = 0; f.n_losses = 2;
-      f.loss_host = ring_only ? nullptr : c->loss_host_dev;
-      f.Ph = c->Ph.p; f.Th = c->Th.p;
-      f.loss_div = (float)B; f.log_alpha_idx = -1; f.auto_entropy = 0;
-      f.err_skip = kErrSkipAll; f.err_nopolyak = kErrActLike;
+      fill(l6.b.adam, opt_step(c, true, B, o.use_ring, host_words));
     }
     if (ride_b) {   // the next update's random.sample rides in L6 (placement B)
       l6.b.ride.kind = 1; l6.b.ride.nblocks = 1;
       l6.b.ride.tbl_log2 = mt_sample_tbl_log2(B, true);
-      l6.b.ride.mt = mt_args(c, B, batch_bufs(c, parity ^ 1));
+      l6.b.ride.mt = mt_args(c, B, batch_bufs(c, o.ride.parity ^ 1));
     }
-    if (phase_mask != 7) {   // data parallel: this update's error flags ride in the critic collective
-      l6.b.err_flags = c->dp_sharding_now ? c->dp_flags.p : G + c->q_end;
+    if (!fused()) {   // data parallel: this update's error flags ride in the critic collective
+      l6.b.err_flags = err_flags();
       l6.b.err_word = &c->sc.p->err;
       check_span(l6.b.err_flags, kDpFlagN - 1, "error flags");
     }
     run(l6, fuse ? "gemm_L6_critic_dW_adam" : "gemm_L6_critic_dW1");
   }
-  if (phase_mask & 2) {
-   const bool fuse = phase_mask == 7 && !c->clip_on;
-   if (!fuse && !c->dp_sharding_now) {   // (sharded: enqueue_dp takes the critic step)
-    // critic Adam (+ Polyak, + q-loss finalisation)
-    AdamArgs ad = dp_adam_args(c, true, B, grad_scale, use_ring);
-    if (polyak_ride) { ad.tgt = nullptr; ad.tgth = nullptr; }   // (Polyak: in L12)
-    if (phase_mask == 7) {   // the clipped single-GPU update: in L6's place (no collective, no
-      ad.err_flags = nullptr;             // flags; the early error word for the synchronous step)
-      ad.loss_host = ring_only ? nullptr : c->loss_host_dev;
+
+  // Phase 1: the critics' optimizer step where no fused level or sharded sequence takes it, the
+  // updated critics on (s, a~), the actor backward and every policy weight gradient (L7 - L13)
+  void enqueue_actor_phase() const {
+    const Linear(&q)[2][4] = c->q_fc;
+    if (!fuse && !o.ride.sharded) {
+      // critic Adam (+ Polyak, + q-loss finalisation).  The clipped single-GPU update: in L6's
+      // place (no collective, no flags; the early error word for the synchronous step)
+      AdamArgs ad = dp_adam_args(c, true, opt_step(c, true, B, o.use_ring, host_words), o.grad_scale,
+                                 fused() ? nullptr : err_flags());
+      if (polyak_ride) { ad.tgt = nullptr; ad.tgth = nullptr; }   // (Polyak: in L12)
+      run_adam(ad, true, polyak_ride ? "adam_critic" : "adam_critic_polyak");
     }
-    const char* name = polyak_ride ? "adam_critic" : "adam_critic_polyak";
-    if (c->clip_on) {
-      enqueue_clip_adam(c, ad, true, name, s);
-    } else if (mark(c, name)) {
-      ad.tl = c->tl_cur;
-      launch_adam(ad, s);
-    }
-   }
-    // L7/L8 (.. L8b): updated critics on [s|1|a~] (head dot partials: slots 4 / 5)
+    // L7/L8 (.. L8b): updated critics on [s|1|a~]
     const float* xa = E(bb.x2, (size_t)B * Kx);
+    const CriticPass act{xa, false, c->hqa, 4};
     Level l7;
-    for (int i = 0; i < 2; ++i)
-      l7.add(fw(gd(xa, Kx, 1, W(q[i][0]), Kx, 1, E(c->hqa[0].p, (size_t)i * Hd), 2 * Hd, B, H, S + A + 1, EPI_RELU)));
+    add_critic_fc1(l7, act);
     std::vector<Level> l8s;   // L8 (.. L8b)
     for (int l = 1; l < nh; ++l) {
       Level lv;
-      for (int i = 0; i < 2; ++i) {
-        GemmDesc g = fw(gd_fwd_h(E(c->hqa[l - 1].p, (size_t)i * Hd), 2 * Hd, W(q[i][l]), Hd,
-                                 E(c->hqa[l].p, (size_t)i * Hd), 2 * Hd, B, H, H));
-        if (l == L) g = with_dot(g, W(q[i][nh]), 4 + i);
-        lv.add(g);
-      }
+      add_critic_hidden(lv, act, l);
       l8s.push_back(lv);
     }
-    // L9: dha[L-1] = (dha[L] W[L]) * relu'(ha[L-1]), with the actor rows folded in: the
-    // prologue finishes qa1, qa2 (dot partials), min (ties 1/2 : 1/2), policy-loss
-    // partials, step counters; dha[L] = dqa * w_head * [ha[L] > 0] is formed on the fly
+    // L9: dha[L-1] with the actor rows folded in: the prologue finishes qa1, qa2 (dot partials),
+    // min (ties 1/2 : 1/2), policy-loss partials, step counters
     Level l9;
-    for (int i = 0; i < 2; ++i) {
-      GemmDesc g = gd(E(c->hqa[L].p, (size_t)i * Hd), 2 * Hd, 1, W(q[i][L]), Hd, 0, c->dha[L - 1].p + i * H, 2 * H,
-                      B, H, H, EPI_MASK, E(c->hqa[L - 1].p, (size_t)i * Hd), 2 * Hd);
-      g.axk = 1; g.ax_slot = i; g.ax_w = W(q[i][nh]);
-      l9.add(dh(g));
-    }
-    {
-      RowsFuse& rf = l9.b.rows;
-      rf.kind = 2; rf.part = dotp(4); rf.nparts = c->nparts; rf.B = B;
-      rf.logp = c->logp.p + B; rf.sc = c->sc.p; rf.loss_part = c->lpart_a.p;
-      if (c->cfg.auto_entropy) {
-        rf.alpha_grad = G + c->la_idx; rf.logp_part = c->lp_part.p;
-        rf.n_lp = (2 * B + heads_rows_per_wg(2 * B) - 1) / heads_rows_per_wg(2 * B);
-        rf.target_entropy = (float)(-A);
-      }
+    RowsFuse& rf = add_critic_dh_rows(l9, act, c->dha, 2, false);
+    rf.logp = c->logp.p + B; rf.loss_part = c->lpart_a.p;
+    if (c->cfg.auto_entropy) {
+      rf.alpha_grad = G + c->la_idx; rf.logp_part = c->lp_part.p;
+      rf.n_lp = (2 * B + heads_rows_per_wg(2 * B) - 1) / heads_rows_per_wg(2 * B);
+      rf.target_entropy = (float)(-A);
     }
     // (decided on the complete level: launch_gemm picks the kernel from it)
     // 2 hidden layers: the dL/da GEMM (over both critics' dha1, K = 2H) folds into L9's
@@ -1474,16 +1532,13 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
     std::vector<Level> l9bs;  // L9b (3 hidden layers)
     for (int l = L - 1; l >= 1; --l) {
       Level lv;
-      for (int i = 0; i < 2; ++i)
-        lv.add(dh(gd(c->dha[l].p + i * H, 2 * H, 1, W(q[i][l]), Hd, 0, c->dha[l - 1].p + i * H, 2 * H,
-                     B, H, H, EPI_MASK, E(c->hqa[l - 1].p, (size_t)i * Hd), 2 * Hd)));
+      add_critic_dh(lv, act, c->dha, l);
       l9bs.push_back(lv);
     }
     // L10: dL/da over both critics (K = 2H) + sample backward -> dhead
     GemmDesc da = gd(c->dha[0].p, 2 * H, 1, W(q[0][0]) + S + 1, Kx, 0, nullptr, 0, B, A, 2 * H);
     validate(da);
     // ... and, for the same rows, dhp[L] = (dhead Whead) * relu'(hp[L]) (policy heads backward)
-    auto hpa = [&](int l) { return E(c->hp[l].p, (size_t)B * Hd); };   // actor rows
     SampleBwdArgs sb{};
     sb.cache = c->cache.p + (size_t)B * 3 * A; sb.eps = c->eps.p + (size_t)B * A;
     sb.dhead = c->dhead.p; sb.lddh = c->lddh; sb.A = A; sb.B = B; sb.sc = c->sc.p;
@@ -1494,7 +1549,6 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
     check_span(sb.Wh, (int64_t)(2 * A - 1) * Hd + H - 1, "Whead");
     // L11 (3 hidden layers) .. L12: dhp[l-1] = (dhp[l] Wpi[l]) * relu'(hp[l-1]);
     // L13: every policy dW (+ Adam, alpha step, policy loss, loss ring when fused)
-    auto pdst = [&](const Linear& l) { return fuse ? P + l.off : dW(l); };
     const int pepi = fuse ? EPI_ADAM : EPI_STORE;
     std::vector<Level> l11s;
     for (int l = L; l >= 2; --l) {
@@ -1510,92 +1564,77 @@ static void enqueue_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int ph
       // (profiles/r05/ride_rows_ab; the ride's 22 MB cost L12 ~8 us either way)
       const int rows_per_block = 16;   // (8 waves)
       l12.b.ride.kind = 2; l12.b.ride.nblocks = (B + rows_per_block - 1) / rows_per_block;
-      l12.b.ride.ga = gather_args(c, B, batch_bufs(c, parity ^ 1), false);
+      l12.b.ride.ga = gather_args(c, B, batch_bufs(c, o.ride.parity ^ 1), false);
     }
     // same level structure fused or not: identical reduction order
-    l13.add(dwx(gd_dw_h(c->dhead.p, c->lddh, hpa(L), Hd, pdst(c->p_head), Hd, 2 * A, H, B, pepi, 0)));
+    l13.add(dwx(gd_dw_h(c->dhead.p, c->lddh, hpa(L), Hd, dst(c->p_head), Hd, 2 * A, H, B, pepi, 0)));
     for (int l = L; l >= 1; --l)
-      l13.add(dwx(gd_dw_h(c->dhp[l].p, H, hpa(l - 1), Hd, pdst(c->p_fc[l]), Hd, H, H, B, pepi, 0)));
-    l13.add(dwx(gd(c->dhp[0].p, H, 0, xa, Kx, 0, pdst(c->p_fc[0]), c->p_fc[0].ld, H, S + 1, B, pepi)));
+      l13.add(dwx(gd_dw_h(c->dhp[l].p, H, hpa(l - 1), Hd, dst(c->p_fc[l]), Hd, H, H, B, pepi, 0)));
+    l13.add(dwx(gd(c->dhp[0].p, H, 0, xa, Kx, 0, dst(c->p_fc[0]), c->p_fc[0].ld, H, S + 1, B, pepi)));
     if (fuse) {
-      AdamFuse& f = l13.b.adam;
       l13.b.has_adam = 1;
-      f.P = P; f.M = c->M.p; f.V = c->V.p; f.T = nullptr; f.G = c->keep_grads ? G : nullptr;
-      f.t_base = 0;
-      f.lr = (float)c->cfg.lr; f.beta1 = 0.9f; f.beta2 = 0.999f; f.eps = 1e-8f; f.tau = 0.f;
-      f.step_offset = 0; f.sc = c->sc.p;
-      f.loss_part = c->lpart_a.p; f.n_part = nb; f.loss_slot0 = 2; f.n_losses = 1;
-      f.loss_host = ring_only ? nullptr : c->loss_host_dev;
-      f.Ph = c->Ph.p; f.Th = c->Th.p;
-      f.loss_div = (float)B; f.log_alpha_idx = c->la_idx; f.auto_entropy = c->cfg.auto_entropy;
-      f.log_alpha_grad = G + c->la_idx;
-      f.loss_ring = use_ring ? c->ring.p : nullptr; f.ring = c->ring_slots;
-      f.done_word = ring_only ? nullptr : reinterpret_cast<int*>(c->loss_host_dev + 4);
-      f.err_skip = ~0; f.err_nopolyak = 0;
+      fill(l13.b.adam, opt_step(c, false, B, o.use_ring, host_words));
     }
-    if (polyak_ride) {   // (polyak_ride: the critic Adam above left the targets alone)
-      PolyakArgs& pk = l12.b.ride.pk;
-      pk.T = c->T.p; pk.P = P + c->q_begin; pk.Th = c->Th.p;
-      pk.n4 = (c->q_end - c->q_begin) / 4; pk.tau = (float)c->cfg.tau; pk.sc = c->sc.p;
+    if (polyak_ride) {   // (polyak_ride: the critic step above or in L6 left the targets alone)
+      l12.b.ride.pk = polyak_args(c);
       l12.b.ride.pk_blocks = std::max(8, 248 - ((B + 31) / 32) * ((H + 31) / 32)) / 8 * 8;
     }
-    if (ride_next && !ride_b) {
+    if (o.ride.ride_next && !ride_b) {
       // the next update's random.sample rides in L12 (128 tiles: idle CUs)
-      const BatchBufs nb2 = batch_bufs(c, parity ^ 1);
+      const BatchBufs nb2 = batch_bufs(c, o.ride.parity ^ 1);
       l12.b.ride.kind = 1; l12.b.ride.nblocks = 1;
       l12.b.ride.tbl_log2 = mt_sample_tbl_log2(B);
       l12.b.ride.mt = mt_args(c, B, nb2);
-      if (c->pf_save) l12.b.ride.mt.mt_save = c->mt_pf.p;   // (a single update's draw ahead)
+      if (o.ride.save_mt) l12.b.ride.mt.mt_save = c->mt_pf.p;   // (a draw ahead)
       // ... and its gather in L13
       l13.b.ride.kind = 2; l13.b.ride.nblocks = 16;
       l13.b.ride.ga = gather_args(c, B, nb2, false);
     }
-    {
-      run(l7, "gemm_L7_act_fc1");
-      for (size_t i = 0; i < l8s.size(); ++i) run(l8s[i], i == 0 ? "gemm_L8_act_fc2" : "gemm_L8b_act_fc3");
-      // (no side-stream fork: every cross-stream edge cost the chain ~10 us, enqueue_many)
-      if (c->stats_on) enqueue_stats(c, B, bb, s);
-      run(l9, "gemm_L9_act_dh1");
-      for (Level& lv : l9bs) run(lv, "gemm_L9b_act_dh");
-      if (fold_dlda) {
-        if (mark(c, "sample_bwd_tail_dhp2", 2.0 * B * (2.0 * A) * H)) {
-          sb.tl = c->tl_cur;
-          launch_sample_bwd_tail(c->pa.p, 2 * c->nparts, sb, s);
-        }
-      } else if (mark(c, "gemm_L10_dlda_sample_bwd_dhp2", 2.0 * B * A * (2.0 * H) + 2.0 * B * (2.0 * A) * H)) {
+    run(l7, "gemm_L7_act_fc1");
+    for (size_t i = 0; i < l8s.size(); ++i) run(l8s[i], i == 0 ? "gemm_L8_act_fc2" : "gemm_L8b_act_fc3");
+    // (no side-stream fork: every cross-stream edge cost the chain ~10 us, enqueue_many)
+    if (c->stats_on) enqueue_stats(c, B, bb, s);
+    run(l9, "gemm_L9_act_dh1");
+    for (Level& lv : l9bs) run(lv, "gemm_L9b_act_dh");
+    if (fold_dlda) {
+      if (mark(c, "sample_bwd_tail_dhp2", 2.0 * B * (2.0 * A) * H)) {
         sb.tl = c->tl_cur;
-        launch_gemm_sample_bwd(da, sb, s);
+        launch_sample_bwd_tail(c->pa.p, 2 * c->nparts, sb, s);
       }
-      for (Level& lv : l11s) run(lv, "gemm_L11_pi_dhp");
-      run(l12, "gemm_L12_pi_dhp1");
+    } else if (mark(c, "gemm_L10_dlda_sample_bwd_dhp2", 2.0 * B * A * (2.0 * H) + 2.0 * B * (2.0 * A) * H)) {
+      sb.tl = c->tl_cur;
+      launch_gemm_sample_bwd(da, sb, s);
     }
+    for (Level& lv : l11s) run(lv, "gemm_L11_pi_dhp");
+    run(l12, "gemm_L12_pi_dhp1");
     run(l13, fuse ? "gemm_L13_pi_dW_adam" : "gemm_L13_pi_dW1");
     // (off the chain in front of L6: nothing of this update reads the priorities)
-    if (fb && fork_r < 0) enqueue_feedback(c, B, bb, s);
+    if (fb && o.ride.fork_r < 0) enqueue_feedback(c, B, bb, s);
   }
-  if ((phase_mask & 4) && (phase_mask != 7 || c->clip_on)) {
-    AdamArgs ad = dp_adam_args(c, false, B, grad_scale, use_ring);
-    if (phase_mask == 7 && !ring_only) {   // the clipped single-GPU update: in L13's place, the
-      ad.loss_host = c->loss_host_dev;     // update's last scalar work (the synchronous step's
-      ad.done_word = reinterpret_cast<int*>(c->loss_host_dev + 4);   // losses and done word)
-    }
-    if (c->clip_on) {
-      enqueue_clip_adam(c, ad, false, "adam_actor_alpha", s);
-    } else if (mark(c, "adam_actor_alpha")) {
-      ad.tl = c->tl_cur;
-      launch_adam(ad, s);
-    }
-  }
-}
 
-// Explicit batch-set control for a phase-split update (the data-parallel driver's
-// captured sequences): parity = this update's minibatch buffer set, have_batch = its
-// indices/rows were produced by the previous update's rides, ride_next = produce the
-// next update's (in the phase-1 launches).
-struct PhaseRide {
-  int parity = 0;
-  bool have_batch = false, ride_next = false;
+  // Phase 2: the actor's optimizer step (+ the alpha step, the policy loss, the loss ring) where L13
+  // did not take it (clipped single-GPU update: the synchronous step's losses and done word too)
+  void enqueue_actor_step() const {
+    run_adam(dp_adam_args(c, false, opt_step(c, false, B, o.use_ring, host_words), o.grad_scale, nullptr),
+             false, "adam_actor_alpha");
+  }
 };
+
+static void enqueue_update(sacmi_ctx* c, const UpdateOpts& o) {
+  const UpdatePlan p{c, o};
+  REQUIRE(!p.fb || p.fused(), SACMI_ESTATE, "prioritized feedback needs the fused update");
+  // every Adam step of this update but the sharded data-parallel form's own (enqueue_dp steps
+  // this rank's chunks) reads and writes the whole of M, V
+  if ((o.phase_mask & (kPhaseActor | kPhaseActorStep)) && !o.ride.sharded) require_moments_whole(c);
+  REQUIRE(!(own_gather(c) && o.ride.ride_next), SACMI_ESTATE,
+          "observation normalisation or n-step returns on: no gather rides along or is drawn ahead");
+  REQUIRE(!p.ride_b || (p.fused() && ride_b_possible(c, o.B)), SACMI_ESTATE,
+          "no ride-along placement for this batch");
+  c->site_counter = 0;
+  if (o.phase_mask & kPhaseCritic) p.enqueue_critic_phase();
+  if (o.phase_mask & kPhaseActor) p.enqueue_actor_phase();
+  if ((o.phase_mask & kPhaseActorStep) && !p.fuse) p.enqueue_actor_step();
+}
 
 // The fill a captured update depends on: none for uniform replay and for the fused PER
 // sampler (both read it from the device scalars); the unfused PER sequence of very large
@@ -1608,8 +1647,10 @@ static int64_t per_graph_len(const sacmi_ctx* c) {
 // n consecutive fused updates (sacmi_step_many_async, the timeline's replica of it):
 // the next update's sampling + gather ride along in this update's launches where they fit
 // (uniform replay, batch <= ~2k), else run on the side stream concurrently with it
-static void enqueue_many(sacmi_ctx* c, int B, int dev_idx, int dev_eps, bool use_ring, int reps,
-                         const PhaseRide& pr = {}) {
+static void enqueue_many(sacmi_ctx* c, UpdateOpts u, int reps) {
+  const int B = u.B, dev_idx = u.dev_idx;
+  const PhaseRide pr = u.ride;   // (the launch's: a batch drawn ahead to take and / or to make)
+  u.ride = PhaseRide{};
   const bool ride = reps > 1 && dev_idx && (ride_possible(c, B) || ride_b_possible(c, B));
   // prioritized replay only: its sampler is long and mostly serial (the numpy-MT uniforms
   // of one workgroup, the 8192-row chunk trees), so overlapping it wins (config 3: 768 ->
@@ -1641,18 +1682,14 @@ static void enqueue_many(sacmi_ctx* c, int B, int dev_idx, int dev_eps, bool use
     const bool fb = feedback_on(c, dev_idx);
     for (int r = 0; r < reps; ++r) {
       if (r > 0) CHECK_HIP(hipStreamWaitEvent(c->stream, c->side_ev[2 * r + 1], 0));
+      u.ride.parity = r & 1;
+      u.ride.have_batch = true;
       if (fb) {
-        enqueue_update(c, B, dev_idx, dev_eps, 7, 1.f, use_ring, r & 1, true, false,
-                       r + 1 < reps ? r : -1);
-        continue;
+        u.ride.fork_r = r + 1 < reps ? r : -1;
+      } else if (r + 1 < reps) {
+        fork_next_draw(c, B, r, false);
       }
-      if (r + 1 < reps) {
-        CHECK_HIP(hipEventRecord(c->side_ev[2 * r], c->stream));
-        CHECK_HIP(hipStreamWaitEvent(c->side_stream, c->side_ev[2 * r], 0));
-        enqueue_sample_gather(c, B, (r + 1) & 1, true, c->side_stream, "_next");
-        CHECK_HIP(hipEventRecord(c->side_ev[2 * r + 3], c->side_stream));
-      }
-      enqueue_update(c, B, dev_idx, dev_eps, 7, 1.f, use_ring, r & 1, true, false);
+      enqueue_update(c, u);
     }
     return;
   }
@@ -1661,53 +1698,55 @@ static void enqueue_many(sacmi_ctx* c, int B, int dev_idx, int dev_eps, bool use
   const int p0 = pr.have_batch ? pr.parity : 0;
   for (int r = 0; r < reps; ++r) {
     const bool last_ahead = r + 1 == reps && pr.ride_next;
-    c->pf_save = last_ahead;
-    enqueue_update(c, B, dev_idx, dev_eps, 7, 1.f, use_ring, ride || pr.have_batch ? ((p0 + r) & 1) : 0,
-                   (ride && r > 0) || (r == 0 && pr.have_batch), (ride && r + 1 < reps) || last_ahead);
-    c->pf_save = false;
+    u.ride.parity = ride || pr.have_batch ? ((p0 + r) & 1) : 0;
+    u.ride.have_batch = (ride && r > 0) || (r == 0 && pr.have_batch);
+    u.ride.ride_next = (ride && r + 1 < reps) || last_ahead;
+    u.ride.save_mt = last_ahead;
+    enqueue_update(c, u);
   }
 }
 
 // What one launch of run_update puts on the stream (its graph's content).  Consecutive fused
 // updates hand the next update's sampling + gather to ride-along workgroups of the current one
-static void enqueue_launch(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_mask,
-                           float grad_scale, bool use_ring, int reps, const PhaseRide& pr) {
-  if (phase_mask == 5) {   // phase 2 of the previous update, then phase 0 of the next
-    enqueue_update(c, B, dev_idx, dev_eps, 4, grad_scale, use_ring, pr.parity ^ 1);
-    enqueue_update(c, B, dev_idx, dev_eps, 1, grad_scale, use_ring, pr.parity, pr.have_batch);
-    return;
+static void enqueue_launch(sacmi_ctx* c, UpdateOpts u, int reps) {
+  if (u.phase_mask == kPhaseStepThenCritic) {   // (the step reads no batch set: the ride is the critic phase's)
+    u.phase_mask = kPhaseActorStep;
+    enqueue_update(c, u);
+    u.phase_mask = kPhaseCritic;
+    enqueue_update(c, u);
+  } else if (u.phase_mask != kPhaseFused) {   // one phase of a split update
+    enqueue_update(c, u);
+  } else if (reps == 1 && (u.ride.ride_next || u.ride.have_batch)) {   // one fused update drawing the next one's batch ahead
+    u.ride.save_mt = true;
+    enqueue_update(c, u);
+  } else {
+    enqueue_many(c, u, reps);
   }
-  if (phase_mask != 7) {   // one phase of a split update
-    enqueue_update(c, B, dev_idx, dev_eps, phase_mask, grad_scale, use_ring, pr.parity,
-                   pr.have_batch, pr.ride_next);
-    return;
-  }
-  if (reps == 1 && (pr.ride_next || pr.have_batch)) {   // one fused update drawing the next one's batch ahead
-    c->pf_save = true;
-    enqueue_update(c, B, dev_idx, dev_eps, 7, grad_scale, use_ring, pr.parity, pr.have_batch, pr.ride_next);
-    c->pf_save = false;
-    return;
-  }
-  enqueue_many(c, B, dev_idx, dev_eps, use_ring, reps, pr);
+}
+
+// GraphKey::phase_mask of a launch: the phases and every setting its graph's content depends on
+static int graph_flags(const sacmi_ctx* c, const UpdateOpts& u) {
+  const PhaseRide& pr = u.ride;
+  return u.phase_mask | (u.grad_scale != 1.f ? kKeyGradScale : 0) | (c->keep_grads ? kKeyKeepGrads : 0) |
+         (pr.parity ? kKeyParity : 0) | (pr.have_batch ? kKeyHaveBatch : 0) | (pr.ride_next ? kKeyRideNext : 0) |
+         (c->mb_graph ? kKeyMailbox : 0) | (c->per_feedback ? kKeyFeedback : 0) |
+         (c->stats_on ? kKeyStats : 0) | (c->clip_on ? kKeyClip : 0) | (obs_norm_on(c) ? kKeyObsNorm : 0) |
+         (nstep_on(c) ? kKeyNStep : 0) | (reward_norm_on(c) ? kKeyRewardNorm : 0);
 }
 
 // what run_update does before it enqueues (before any state changes; enqueue_update)
 static void begin_update(sacmi_ctx* c, int dev_idx, int phase_mask) {
-  REQUIRE(!c->per_feedback || (dev_idx && phase_mask == 7), SACMI_ESTATE,
+  REQUIRE(!c->per_feedback || (dev_idx && phase_mask == kPhaseFused), SACMI_ESTATE,
           "prioritized feedback is on: the update samples on the device (no staged indices, "
           "no phase-split or data-parallel update)");
-  if (phase_mask & 6) require_moments_whole(c);
-  c->pf_save = false;
+  if (phase_mask & (kPhaseActor | kPhaseActorStep)) require_moments_whole(c);
   if (!c->mb_graph) mb_flush(c);   // (mb_graph: this update's sampler takes them)
   c->inflight = true;
 }
 
-static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_mask,
-                       float grad_scale, bool use_ring, int reps = 1, PhaseRide pr = {}) {
-  begin_update(c, dev_idx, phase_mask);
-  auto enqueue_all = [&]() {
-    enqueue_launch(c, B, dev_idx, dev_eps, phase_mask, grad_scale, use_ring, reps, pr);
-  };
+static void run_update(sacmi_ctx* c, const UpdateOpts& u, int reps = 1) {
+  begin_update(c, u.dev_idx, u.phase_mask);
+  auto enqueue_all = [&]() { enqueue_launch(c, u, reps); };
   // the caller is capturing this stream into its own graph (e.g. torch.cuda.graph around
   // a data-parallel update and its collectives): enqueue into that capture directly
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1717,25 +1756,11 @@ static void run_update(sacmi_ctx* c, int B, int dev_idx, int dev_eps, int phase_
     CHECK_HIP(hipGetLastError());
     return;
   }
-  GraphKey key{B, dev_idx, dev_eps,
-               phase_mask | (grad_scale != 1.f ? 8 : 0) | (c->keep_grads ? 16 : 0) |
-                   (pr.parity ? 32 : 0) | (pr.have_batch ? 64 : 0) | (pr.ride_next ? 128 : 0) |
-                   (c->mb_graph ? 256 : 0) | (c->per_feedback ? 512 : 0) |
-                   (c->stats_on ? 1024 : 0) | (c->clip_on ? 2048 : 0) | (obs_norm_on(c) ? 4096 : 0) |
-                   (nstep_on(c) ? 8192 : 0) | (reward_norm_on(c) ? 16384 : 0),
-               use_ring ? c->ring_slots : 0,
-               per_graph_len(c), reps};
+  GraphKey key{u.B, u.dev_idx, u.dev_eps, graph_flags(c, u),
+               u.use_ring ? c->ring_slots : 0, per_graph_len(c), reps};
   auto it = c->graphs.find(key);
   if (it == c->graphs.end()) it = c->graphs.emplace(key, capture_graph(c, enqueue_all)).first;
   CHECK_HIP(hipGraphLaunch(it->second, c->stream));
-}
-
-// the phase-split and data-parallel updates of a context in feedback mode: each rank would
-// write its own minibatch's priorities into its own replica of the array (sharded
-// priorities are not built)
-static void refuse_feedback(const sacmi_ctx* c) {
-  REQUIRE(!(c && c->per_feedback), SACMI_ESTATE,
-          "prioritized feedback is on: no phase-split or data-parallel update");
 }
 
 static void check_batch(sacmi_ctx* c, int B) {
@@ -1906,12 +1931,15 @@ static void loopback_flags(sacmi_ctx* c, float* f, hipStream_t s) {
   if (e && std::atoi(e) != 0) fill_checked(f, 1, (float)c->dp_world + 1.f, s);
 }
 
-static void dp_shard_adam(sacmi_ctx* c, bool critic, int B, int r, bool use_ring) {
+// Rank r's share of one range's step in the sharded form: the range's Adam launch cut to the
+// rank's chunk (the losses leave through the ring)
+static AdamArgs dp_shard_adam(const sacmi_ctx* c, bool critic, int B, int r) {
   const int W = c->dp_world;
-  const int64_t b = critic ? c->q_begin : c->pi_begin, e = critic ? c->q_end : c->total;
-  const int64_t ch = shard_chunk(e - b, W), lo = b + r * ch, hi = std::min(e, lo + ch);
-  AdamArgs ad = dp_adam_args(c, critic, B, loopback_one_rank(c) ? 1.f : 1.f / (float)W, use_ring);
-  ad.tgt = nullptr; ad.tgth = nullptr;   // Polyak: its own pass over the gathered critics
+  const ParamRange pr = param_range(c, critic);
+  const int64_t ch = shard_chunk(pr.end - pr.begin, W), lo = pr.begin + r * ch, hi = std::min(pr.end, lo + ch);
+  AdamArgs ad = dp_adam_args(c, critic, opt_step(c, critic, B, true, false),
+                             loopback_one_rank(c) ? 1.f : 1.f / (float)W, critic ? c->dp_flags.p : nullptr);
+  ad.tgt = nullptr; ad.tgth = nullptr;   // Polyak: in L12, or its own pass over the gathered critics
   const AdamArgs full = ad;
   ad.nseg = 0; ad.total = 0;
   for (int i = 0; i < full.nseg; ++i) {
@@ -1923,20 +1951,20 @@ static void dp_shard_adam(sacmi_ctx* c, bool critic, int B, int r, bool use_ring
   }
   if (!critic && !(c->la_idx >= lo && c->la_idx < hi)) ad.log_alpha_idx = -1;   // (its owner's)
   if (r != c->dp_rank) { ad.n_losses = 0; ad.loss_ring = nullptr; }   // (loopback's other ranks)
-  launch_adam(ad, c->stream);
+  return ad;
 }
 
-static void enqueue_dp_sharded(sacmi_ctx* c, int B, int n) {
+// n data-parallel updates, each: the critic phase, the collective over the critic gradients, the
+// actor phase (all-reduce form: the critic's Adam step in front), the collective over the actor
+// gradients; the actor's step runs in front of the next critic phase.  Sharded form (ZeRO-1):
+// reduce-scatters, each followed by Adam on this rank's chunk and an all-gather of the parameters
+static void enqueue_dp(sacmi_ctx* c, int B, int n) {
   const int W = c->dp_world;
+  const bool sharded = c->dp_shard;
   const bool ride = n > 1 && ride_possible(c, B);
   hipStream_t s = c->stream;
-  auto range = [&](bool critic, int64_t& b, int64_t& e) {
-    b = critic ? c->q_begin : c->pi_begin;
-    e = critic ? c->q_end : c->total;
-  };
   auto reduce_scatter = [&](bool critic) {
-    int64_t b, e;
-    range(critic, b, e);
+    const auto [b, e] = param_range(c, critic);
     const int64_t ch = shard_chunk(e - b, W);
     float* g = c->G.p + b;
     // the critic's error flags to every rank (the reduce-scatter delivers chunk r only): an
@@ -1965,16 +1993,12 @@ static void enqueue_dp_sharded(sacmi_ctx* c, int B, int n) {
     (void)mark(c, critic ? "adam_critic_shard" : "adam_actor_shard");
     // (SACMI_DP_LOOPBACK_ONE_RANK: timing only — rank 0's chunk alone, the per-rank work
     // of a `world`-rank run minus its collectives; the other chunks are left unstepped)
-    const bool one_rank = loopback_one_rank(c);
-    if (c->dp_loopback && !one_rank) {
-      for (int r = 0; r < W; ++r) dp_shard_adam(c, critic, B, r, true);
-    } else if (c->dp_loopback) {
-      dp_shard_adam(c, critic, B, 0, true);
-    } else {
-      dp_shard_adam(c, critic, B, c->dp_rank, true);
+    if (c->dp_loopback && !loopback_one_rank(c)) {
+      for (int r = 0; r < W; ++r) launch_adam(dp_shard_adam(c, critic, B, r), s);
+    } else {   // (the loopback's rank is 0)
+      launch_adam(dp_shard_adam(c, critic, B, c->dp_rank), s);
     }
-    int64_t b, e;
-    range(critic, b, e);
+    const auto [b, e] = param_range(c, critic);
     const int64_t ch = shard_chunk(e - b, W);
     (void)mark(c, critic ? "all_gather_critic_params" : "all_gather_actor_params");
     if (!c->dp_loopback) {
@@ -1984,75 +2008,47 @@ static void enqueue_dp_sharded(sacmi_ctx* c, int B, int n) {
     if (c->Ph.p) to_bf16_checked(c->Ph.p + b, c->P.p + b, e - b, s);
     if (!critic && c->cfg.auto_entropy) launch_alpha_sync(c->sc.p, c->P.p + c->la_idx, ~0, s);
   };
-  // Polyak rides in phase 1's L12 where it can (enqueue_update: polyak_ride), else its own pass
-  const bool pk_ride = !act16_on(c, B) &&
-                       (int64_t)((B + 31) / 32) * ((c->H + 31) / 32) <= 192;
-  c->dp_sharding_now = true;
-  if (!c->dp_loopback && W > 1) c->moments_sharded = true;
-  if (loopback_one_rank(c) && W > 1) c->moments_partial = true;
-  try {
-    int parity = 0;
-    bool have = false;
-    for (int r = 0; r < n; ++r) {
-      if (r > 0) step(false);                                             // previous actor step
-      enqueue_update(c, B, 1, 1, 1, 1.f, true, parity, have);             // phase 0
-      reduce_scatter(true);
-      step(true);
-      if (!pk_ride && mark(c, "polyak")) {
-        PolyakArgs pk{};
-        pk.T = c->T.p; pk.P = c->P.p + c->q_begin; pk.Th = c->Th.p;
-        pk.n4 = (c->q_end - c->q_begin) / 4; pk.tau = (float)c->cfg.tau; pk.sc = c->sc.p;
-        launch_polyak(pk, s);
-      }
-      const bool rn = ride && r + 1 < n;
-      enqueue_update(c, B, 1, 1, 2, 1.f, true, parity, false, rn);        // phase 1 (no critic Adam)
-      reduce_scatter(false);
-      have = rn;
-      parity = rn ? parity ^ 1 : 0;
-    }
-    step(false);
-  } catch (...) {
-    c->dp_sharding_now = false;
-    throw;
-  }
-  c->dp_sharding_now = false;
-}
-
-static void enqueue_dp(sacmi_ctx* c, int B, int n) {
-  if (c->dp_shard) {
-    enqueue_dp_sharded(c, B, n);
-    return;
-  }
-  const float scale = loopback_one_rank(c) ? 1.f : 1.f / (float)c->dp_world;   // (see there)
-  const bool ride = n > 1 && ride_possible(c, B);
-  auto allreduce = [&](int64_t begin, int64_t end) {
-    const bool critic = begin == c->q_begin;
+  auto allreduce = [&](bool critic) {
+    const auto [begin, end] = param_range(c, critic);
     (void)mark(c, critic ? "allreduce_critic_grads" : "allreduce_actor_grads");
     float* g = c->G.p + begin;
     if (c->dp_loopback) {   // what `world` ranks holding identical shards would all-reduce to
       if (!loopback_one_rank(c)) {
-        scale_checked(g, end - begin, (float)c->dp_world, c->stream);
-        if (critic) loopback_flags(c, c->G.p + c->q_end, c->stream);
+        scale_checked(g, end - begin, (float)W, s);
+        if (critic) loopback_flags(c, c->G.p + c->q_end, s);
       }
     } else {
       // the critic range carries the error flags past q_end (kDpFlagN)
       const int64_t n = end - begin + (critic ? kDpFlagN : 0);
-      CHECK_RCCL(rccl().all_reduce(g, g, (size_t)n, ncclFloat32, ncclSum, c->comm, c->stream));
+      CHECK_RCCL(rccl().all_reduce(g, g, (size_t)n, ncclFloat32, ncclSum, c->comm, s));
     }
   };
-  int parity = 0;
-  bool have = false;
+  if (sharded && !c->dp_loopback && W > 1) c->moments_sharded = true;
+  if (sharded && loopback_one_rank(c) && W > 1) c->moments_partial = true;
+  // (all-reduce form: k_adam applies the 1/world; sharded: dp_shard_adam's launches do)
+  UpdateOpts u{B, 1, 1, kPhaseCritic, sharded || loopback_one_rank(c) ? 1.f : 1.f / (float)W, true};
+  u.ride.sharded = sharded;
+  auto phase = [&](int mask) {
+    u.phase_mask = mask;
+    enqueue_update(c, u);
+  };
+  auto actor_step = [&] { sharded ? step(false) : phase(kPhaseActorStep); };
   for (int r = 0; r < n; ++r) {
-    if (r > 0) enqueue_update(c, B, 1, 1, 4, scale, true, parity ^ 1);   // previous phase 2
-    enqueue_update(c, B, 1, 1, 1, scale, true, parity, have);            // phase 0
-    allreduce(c->q_begin, c->q_end);
-    const bool rn = ride && r + 1 < n;
-    enqueue_update(c, B, 1, 1, 2, scale, true, parity, false, rn);        // phase 1
-    allreduce(c->pi_begin, c->total);
-    have = rn;
-    parity = rn ? parity ^ 1 : 0;
+    if (r > 0) actor_step();   // the previous update's
+    phase(kPhaseCritic);
+    sharded ? reduce_scatter(true) : allreduce(true);
+    if (sharded) step(true);
+    // (sharded: Polyak rides in the actor phase's L12 where it can, else its own pass)
+    if (sharded && !polyak_rides(c, B, kPhaseActor) && mark(c, "polyak")) launch_polyak(polyak_args(c), s);
+    u.ride.have_batch = false;
+    u.ride.ride_next = ride && r + 1 < n;
+    phase(kPhaseActor);
+    sharded ? reduce_scatter(false) : allreduce(false);
+    u.ride.have_batch = u.ride.ride_next;     // the next update's critic phase takes the ride's batch
+    u.ride.ride_next = false;
+    u.ride.parity = u.ride.have_batch ? u.ride.parity ^ 1 : 0;
   }
-  enqueue_update(c, B, 1, 1, 4, scale, true, parity);                   // last phase 2
+  actor_step();
 }
 
 // Every rank's chunks of the Adam moments onto every rank, in place (collective; a no-op
@@ -2063,7 +2059,7 @@ static void dp_gather_moments(sacmi_ctx* c) {
   if (!c->moments_sharded || c->dp_loopback || c->dp_world == 1) return;
   const int W = c->dp_world;
   for (int critic = 1; critic >= 0; --critic) {
-    const int64_t b = critic ? c->q_begin : c->pi_begin, e = critic ? c->q_end : c->total;
+    const auto [b, e] = param_range(c, critic != 0);
     const int64_t ch = shard_chunk(e - b, W);
     DevBuf<float> tmp;
     tmp.alloc((size_t)ch * W);
@@ -2827,7 +2823,7 @@ static void run_update_mb(sacmi_ctx* c, int B, int dev_idx, int dev_eps, bool mb
   c->mb_graph = mb_ok && dev_idx && c->mb_pending > 0 && cap == hipStreamCaptureStatusNone &&
                 c->cfg.replay_kind == SACMI_REPLAY_UNIFORM && !pr.have_batch;
   try {
-    run_update(c, B, dev_idx, dev_eps, 7, 1.f, use_ring, 1, pr);
+    run_update(c, UpdateOpts{B, dev_idx, dev_eps, kPhaseFused, 1.f, use_ring, pr});
     pf_end(c, B, pr);
   } catch (...) {
     c->mb_graph = false;
@@ -2935,7 +2931,7 @@ int sacmi_step_many_async(sacmi_ctx* c, int32_t batch, int32_t n_updates) {
     check_device_batch(c, batch);
     REQUIRE(n_updates >= 1 && n_updates <= 256, SACMI_EVALUE, "n_updates must be in [1, 256]");
     const PhaseRide pr = pf_begin(c, batch, true);   // (draws the next launch's batch ahead)
-    run_update(c, batch, 1, 1, 7, 1.f, true, n_updates, pr);
+    run_update(c, UpdateOpts{batch, 1, 1, kPhaseFused, 1.f, true, pr}, n_updates);
     pf_end(c, batch, pr, n_updates);
   });
 }
@@ -3080,12 +3076,6 @@ int sacmi_fetch_grad_norms(sacmi_ctx* c, float* out, int32_t max_rows, int32_t* 
 
 // ---------------------------------------------------------------------------
 // running observation normalisation (obsnorm.hip)
-static void refuse_obs_norm(const sacmi_ctx* c) {
-  REQUIRE(!(c && obs_norm_on(c)), SACMI_ESTATE,
-          "observation normalisation is on: no phase-split or data-parallel update (each rank's "
-          "shard would grow statistics of its own; a collective over the moments is not built)");
-}
-
 static void set_obs_norm(sacmi_ctx* c, int32_t mode, double eps, double clip) {
   REQUIRE(c, SACMI_EVALUE, "null ctx");
   REQUIRE(mode >= 0 && mode <= 2, SACMI_EVALUE, "mode must be 0 (off), 1 (on) or 2 (on, frozen)");
@@ -3252,12 +3242,6 @@ int sacmi_mark_episode_end(sacmi_ctx* c) {
 
 // ---------------------------------------------------------------------------
 // reward scaling and running return normalisation (retnorm.hip)
-static void refuse_reward_norm(const sacmi_ctx* c) {
-  REQUIRE(!(c && reward_norm_on(c)), SACMI_ESTATE,
-          "reward normalisation is on: no phase-split or data-parallel update (each rank's shard "
-          "would grow return statistics of its own; a collective over them is not built)");
-}
-
 static void reward_norm_alloc(sacmi_ctx* c) {
   if (c->rn_state.p) return;
   c->rn_state.alloc(4);
@@ -3389,25 +3373,30 @@ int sacmi_debug_set_done(sacmi_ctx* c, const int64_t* slots, const float* values
   });
 }
 
+// The phase-split and data-parallel updates (and the timeline of the latter's sequence) refuse
+// what only the fused single-GPU update builds; any of them also drops a batch drawn ahead
+static void require_split_update_allowed(sacmi_ctx* c) {
+  REQUIRE(!(c && obs_norm_on(c)), SACMI_ESTATE,
+          "observation normalisation is on: no phase-split or data-parallel update (each rank's "
+          "shard would grow statistics of its own; a collective over the moments is not built)");
+  REQUIRE(!(c && reward_norm_on(c)), SACMI_ESTATE,
+          "reward normalisation is on: no phase-split or data-parallel update (each rank's shard "
+          "would grow return statistics of its own; a collective over them is not built)");
+  pf_touch(c);
+  // (feedback mode: each rank would write its own minibatch's priorities into its own replica
+  // of the array; sharded priorities are not built)
+  REQUIRE(!(c && c->per_feedback), SACMI_ESTATE,
+          "prioritized feedback is on: no phase-split or data-parallel update");
+}
+
 int sacmi_step_phase(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_scale) {
-  return guard([&] {
-    refuse_obs_norm(c);
-    refuse_reward_norm(c);
-    pf_touch(c);
-    refuse_feedback(c);
-    REQUIRE(phase >= 0 && phase <= 3, SACMI_EVALUE, "phase must be 0, 1, 2 or 3");
-    if (phase == 0 || phase == 3) check_device_batch(c, batch);
-    run_update(c, batch, 1, 1, phase == 3 ? 5 : 1 << phase, grad_scale, false);
-  });
+  return sacmi_step_phase_ex(c, batch, phase, grad_scale, 0, 0, 0);   // (set 0, no rides)
 }
 
 int sacmi_step_phase_ex(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_scale,
                         int32_t parity, int32_t have_batch, int32_t ride_next) {
   return guard([&] {
-    refuse_obs_norm(c);
-    refuse_reward_norm(c);
-    pf_touch(c);
-    refuse_feedback(c);
+    require_split_update_allowed(c);
     REQUIRE(phase >= 0 && phase <= 3, SACMI_EVALUE, "phase must be 0, 1, 2 or 3");
     REQUIRE(parity == 0 || parity == 1, SACMI_EVALUE, "parity must be 0 or 1");
     REQUIRE(!(nstep_on(c) && ride_next), SACMI_ESTATE, "n-step returns are on: no gather rides along");
@@ -3418,7 +3407,7 @@ int sacmi_step_phase_ex(sacmi_ctx* c, int32_t batch, int32_t phase, float grad_s
     pr.ride_next = ride_next && phase == 1 && ride_possible(c, batch);
     REQUIRE(!pr.have_batch || ride_possible(c, batch), SACMI_EVALUE,
             "have_batch needs uniform replay with a ride-capable batch size");
-    run_update(c, batch, 1, 1, phase == 3 ? 5 : 1 << phase, grad_scale, false, 1, pr);
+    run_update(c, UpdateOpts{batch, 1, 1, phase == 3 ? kPhaseStepThenCritic : 1 << phase, grad_scale, false, pr});
   });
 }
 
@@ -3469,11 +3458,8 @@ int sacmi_dp_loopback_init(sacmi_ctx* c, int32_t world) {
 
 int sacmi_step_dp(sacmi_ctx* c, int32_t batch, int32_t n_updates) {
   return guard([&] {
-    refuse_obs_norm(c);
-    refuse_reward_norm(c);
+    require_split_update_allowed(c);
     refuse_clip_sharded(c, c->dp_shard && (c->dp_world > 1 || c->dp_loopback || dp_phases_at_world1()));
-    pf_touch(c);
-    refuse_feedback(c);
     mb_flush(c);
     REQUIRE(c->comm || c->dp_loopback, SACMI_ESTATE, "sacmi_allreduce_init has not been called");
     check_device_batch(c, batch);
@@ -3482,7 +3468,7 @@ int sacmi_step_dp(sacmi_ctx* c, int32_t batch, int32_t n_updates) {
     // test_dp_* world-1 and loopback tests), unless SACMI_DP_PHASES_AT_WORLD1 asks for the
     // phase sequence and its collectives anyway
     if (c->dp_world == 1 && !c->dp_loopback && !dp_phases_at_world1()) {
-      run_update(c, batch, 1, 1, 7, 1.f, true, n_updates);
+      run_update(c, UpdateOpts{batch, 1, 1, kPhaseFused, 1.f, true}, n_updates);
       return;
     }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -3665,7 +3651,7 @@ int sacmi_profile_step(sacmi_ctx* c, int32_t batch, int32_t iters, char* names_o
       c->prof = true;
       c->prof_events.clear(); c->prof_names.clear(); c->prof_flops.clear(); c->prof_bytes.clear();
       try {
-        enqueue_update(c, batch, 1, 1, 7, 1.f, false);
+        enqueue_update(c, UpdateOpts{batch});
         (void)mark(c, "end");
       } catch (...) {
         c->prof = false;
@@ -3706,7 +3692,7 @@ int sacmi_profile_sites(sacmi_ctx* c, int32_t batch, int32_t reps, char* names_o
     c->prof_collect = true;
     c->prof_site = 1 << 30;
     try {
-      enqueue_update(c, batch, 1, 1, 7, 1.f, false);
+      enqueue_update(c, UpdateOpts{batch});
     } catch (...) {
       c->prof_collect = false; c->prof_site = -1;
       throw;
@@ -3723,7 +3709,7 @@ int sacmi_profile_sites(sacmi_ctx* c, int32_t batch, int32_t reps, char* names_o
       c->prof_site = i;
       hipGraphExec_t ex;
       try {
-        ex = capture_graph(c, [&] { for (int r = 0; r < reps; ++r) enqueue_update(c, batch, 1, 1, 7, 1.f, false); });
+        ex = capture_graph(c, [&] { for (int r = 0; r < reps; ++r) enqueue_update(c, UpdateOpts{batch}); });
       } catch (...) {
         c->prof_site = -1;
         throw;
@@ -3754,11 +3740,17 @@ int sacmi_profile_sites(sacmi_ctx* c, int32_t batch, int32_t reps, char* names_o
 // warm (unless !warm), then once measured between HIP events.  Sites that launch no stamping kernel (the
 // RCCL all-reduces of the data-parallel sequence) leave no entry.
 extern "C++" {
+// the caller's output arrays of the three timeline entry points (include/sacmi.h)
+struct TimelineOut {
+  int32_t max_kernels;
+  char* names_out; int32_t* kind_out; int32_t* grid_out; int32_t* site_out;
+  double* start_us; double* end_us; double* flops_out; double* bytes_out;
+  int32_t* n_kernels; double* graph_us;
+};
 template <class F>
-static void timeline_of(sacmi_ctx* c, int n_updates, F&& enqueue, int32_t max_kernels,
-                        char* names_out, int32_t* kind_out, int32_t* grid_out, int32_t* site_out,
-                        double* start_us, double* end_us, double* flops_out, double* bytes_out,
-                        int32_t* n_kernels, double* graph_us, bool warm = true) {
+static void timeline_of(sacmi_ctx* c, int n_updates, F&& enqueue, const TimelineOut& out, bool warm = true) {
+  const auto [max_kernels, names_out, kind_out, grid_out, site_out, start_us, end_us, flops_out, bytes_out,
+              n_kernels, graph_us] = out;
   REQUIRE(max_kernels > 0 && names_out && kind_out && grid_out && site_out && start_us && end_us &&
               n_kernels && graph_us, SACMI_EVALUE, "null output");
   CHECK_HIP(hipStreamSynchronize(c->stream));
@@ -3844,14 +3836,15 @@ int sacmi_profile_timeline(sacmi_ctx* c, int32_t batch, int32_t n_updates, int32
                            char* names_out, int32_t* kind_out, int32_t* grid_out, int32_t* site_out,
                            double* start_us, double* end_us, double* flops_out, double* bytes_out,
                            int32_t* n_kernels, double* graph_us) {
+  const TimelineOut out{max_kernels, names_out, kind_out, grid_out, site_out, start_us, end_us,
+                        flops_out, bytes_out, n_kernels, graph_us};
   return guard([&] {
     pf_touch(c);
     mb_flush(c);
     check_device_batch(c, batch);
     REQUIRE(n_updates >= 1 && n_updates <= 256, SACMI_EVALUE, "n_updates must be in [1, 256]");
     // the same update sequence sacmi_step_many_async replays
-    timeline_of(c, n_updates, [&]() { enqueue_many(c, batch, 1, 1, true, n_updates); }, max_kernels, names_out, kind_out, grid_out, site_out, start_us, end_us, flops_out,
-       bytes_out, n_kernels, graph_us);
+    timeline_of(c, n_updates, [&]() { enqueue_many(c, UpdateOpts{batch, 1, 1, kPhaseFused, 1.f, true}, n_updates); }, out);
   });
 }
 
@@ -3859,16 +3852,17 @@ int sacmi_profile_launch_timeline(sacmi_ctx* c, int32_t batch, int32_t n_updates
                                   char* names_out, int32_t* kind_out, int32_t* grid_out, int32_t* site_out,
                                   double* start_us, double* end_us, double* flops_out, double* bytes_out,
                                   int32_t* n_kernels, double* graph_us) {
+  const TimelineOut out{max_kernels, names_out, kind_out, grid_out, site_out, start_us, end_us,
+                        flops_out, bytes_out, n_kernels, graph_us};
   return guard([&] {
     check_device_batch(c, batch);
     REQUIRE(n_updates >= 1 && n_updates <= 256, SACMI_EVALUE, "n_updates must be in [1, 256]");
     // sacmi_step_many_async itself, its graph captured with the stamps and launched once: it
     // takes a batch drawn ahead and draws the next launch's exactly as that call would now
     const PhaseRide pr = pf_begin(c, batch, true);
-    begin_update(c, 1, 7);
-    timeline_of(c, n_updates, [&]() { enqueue_launch(c, batch, 1, 1, 7, 1.f, true, n_updates, pr); },
-                max_kernels, names_out, kind_out, grid_out, site_out, start_us, end_us, flops_out,
-                bytes_out, n_kernels, graph_us, false);
+    begin_update(c, 1, kPhaseFused);
+    timeline_of(c, n_updates, [&]() { enqueue_launch(c, UpdateOpts{batch, 1, 1, kPhaseFused, 1.f, true, pr}, n_updates); },
+                out, false);
     pf_end(c, batch, pr, n_updates);
   });
 }
@@ -3877,17 +3871,16 @@ int sacmi_profile_timeline_dp(sacmi_ctx* c, int32_t batch, int32_t n_updates, in
                               char* names_out, int32_t* kind_out, int32_t* grid_out, int32_t* site_out,
                               double* start_us, double* end_us, double* flops_out, double* bytes_out,
                               int32_t* n_kernels, double* graph_us) {
+  const TimelineOut out{max_kernels, names_out, kind_out, grid_out, site_out, start_us, end_us,
+                        flops_out, bytes_out, n_kernels, graph_us};
   return guard([&] {
-    pf_touch(c);
-    refuse_feedback(c);
+    require_split_update_allowed(c);
     mb_flush(c);
     REQUIRE(c->comm || c->dp_loopback, SACMI_ESTATE, "sacmi_allreduce_init has not been called");
     check_device_batch(c, batch);
     REQUIRE(n_updates >= 1 && n_updates <= 256, SACMI_EVALUE, "n_updates must be in [1, 256]");
     // the sequence sacmi_step_dp replays: phases + the two RCCL all-reduces per update
-    timeline_of(c, n_updates, [&]() { enqueue_dp(c, batch, n_updates); }, max_kernels,
-                names_out, kind_out, grid_out, site_out, start_us, end_us, flops_out, bytes_out,
-                n_kernels, graph_us);
+    timeline_of(c, n_updates, [&]() { enqueue_dp(c, batch, n_updates); }, out);
   });
 }
 

@@ -476,6 +476,8 @@ def test_refusals():
         a.set_obs_norm(1, EPS, CLIP)
         with pytest.raises(L.SacmiError, match=f"sacmi error {L.SACMI_ESTATE}"):
             a.step_dp(B, 1)
+        with pytest.raises(L.SacmiError, match="observation normalisation is on"):
+            a.profile_timeline(B, 1, data_parallel=True)   # (the sequence step_dp would replay)
         after = ctx_state(a, cfg)
         for k in before:
             assert np.array_equal(bits(before[k]), bits(after[k])), k
