@@ -3,7 +3,8 @@
 Bit-exact: sampled indices, numpy MT19937 stream advance, update_priorities (last
 duplicate wins), push-time max priority.  IS weights: within 4 ulp (the reference's
 float32 ``**`` runs through numpy's SIMD pow, which is up to 1 ulp from powf —
-SURVEY §0 C6)."""
+SURVEY §0 C6).  The cdf itself (sum order, scan, search) is pinned bit for bit with boundary
+draws in tests/test_gpu_per_cdf.py; the random draws here do not see a 1-ulp normaliser."""
 import os
 
 import numpy as np
